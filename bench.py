@@ -25,7 +25,13 @@ and the max-over-ranks of the timed region.
 Each rank keeps >= 1.2 GB of distinct resident batches and cycles over them, so
 no timed pass is served from the 256 MiB Infinity Cache.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run measures the headline workload alone: it sets up, warms up, times
+the K steps and prints the result line.  Every other row and leg above (the other
+configs, the roofline's kernel durations, the read probe, the CPU baselines, the
+end-to-end and backend legs) runs with --full, which also writes the detail
+record.  --dump-outputs DIR writes the records the last timed step produced.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -304,7 +310,40 @@ def resident_batches(ctx, key, world, rank, nres):
     return dbs, trs, mine
 
 
-def measure(ctx, dist, key, steps, warmup, rank):
+DUMP_MAX_BYTES = 64 << 20      # all files of one --dump-outputs together
+DUMP_SEED = 0x6D6F7372         # the fixed sample of frames of a larger output
+
+
+def dump_outputs(path: str, key: str, dbs):
+    """--dump-outputs: what the last timed step wrote for its batches `dbs` (in the
+    step's order, frames concatenated), as a caller of the path receives it: the
+    records (16-byte mosrx_result, or the 8-byte mosrx_result8 of the compact rows)
+    one file per field, <field>.npy, and the filter match masks (match.npy) of the
+    fused rows.  32-bit fields as float64, narrower ones as float32 (both exact).
+    An output past DUMP_MAX_BYTES is cut to a fixed, seeded sample of its frames,
+    whose indices go to sample_index.npy."""
+    rec = np.concatenate([d.results8() if key in COMPACT else d.results() for d in dbs])
+    cols = {f: rec[f] for f in rec.dtype.names}
+    if "_cls_bpf" in key:
+        cols["match"] = np.concatenate([d.matches() for d in dbs])
+    cols = {f: a.astype(np.float64 if a.dtype.itemsize > 2 else np.float32) for f, a in cols.items()}
+    n = len(rec)
+    per_frame = sum(a.dtype.itemsize for a in cols.values()) + 8      # (+ the index, when sampled)
+    if n * per_frame > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_BYTES // per_frame - 16, replace=False))
+        cols = {f: a[idx] for f, a in cols.items()}
+        cols["sample_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for f, a in cols.items():
+        np.save(os.path.join(path, f + ".npy"), a)
+    progress(f"outputs of the last timed step: {len(cols)} arrays of {len(next(iter(cols.values())))} of {n} frames "
+             f"in {path}")
+
+
+def measure(ctx, dist, key, steps, warmup, rank, full=True, dump=None):
+    """One workload's timed steps.  full: also the launch durations behind the
+    roofline (runs of their own after the timed steps).  dump: the folder the last
+    timed step's outputs go to (classify rows; rank 0)."""
     kind, batch, ring, label = WORKLOADS[key]
     params = mosrx.default_params(skip_tcp_csum=1 if key.startswith("S64_hdr") else 0)
     ctx.set_params(params)
@@ -335,13 +374,14 @@ def measure(ctx, dist, key, steps, warmup, rank):
         wall = time.perf_counter() - t0     # this rank's region; the max over ranks below
         dist.barrier()
         wall_max = dist.max(wall)
-        kk = 500
-        # the kernel's own duration (each launch stamped by its dispatch, as
-        # rocprofv3 reports it); ops of more than one launch: back to back
-        kern_b2b = median_of(lambda: step_fn(kk, 1) / kk)
-        kern_ms, timing = kernel_duration(lambda: ctx.time_op_dispatch(op, dbs, kk, arg), kern_b2b)
-        kern_iso = None
-        floor_ms = stamp_floor(ctx, dbs[0], kk, timing)
+        kern_ms = kern_b2b = kern_iso = floor_ms = timing = None
+        if full:
+            kk = 500
+            # the kernel's own duration (each launch stamped by its dispatch, as
+            # rocprofv3 reports it); ops of more than one launch: back to back
+            kern_b2b = median_of(lambda: step_fn(kk, 1) / kk)
+            kern_ms, timing = kernel_duration(lambda: ctx.time_op_dispatch(op, dbs, kk, arg), kern_b2b)
+            floor_ms = stamp_floor(ctx, dbs[0], kk, timing)
         frames_per_step, ab_step = batch, ab
         method = f"one launch per batch, batch i on stream i % {STREAMS}"
     elif ring:
@@ -364,11 +404,15 @@ def measure(ctx, dist, key, steps, warmup, rank):
         wall = time.perf_counter() - t0     # this rank's region; the max over ranks below
         dist.barrier()
         wall_max = dist.max(wall)
-        kk = max(16, 4 * len(qs))
-        kern_b2b = median_of(lambda: qs[0].time(kk, qs[1:], kernels=False)[0] / kk)
-        kern_ms, timing = kernel_duration(lambda: qs[0].time_dispatch(kk, qs[1:]), kern_b2b)
-        floor_ms = None
-        _, kern_iso = qs[0].time(min(kk, 32), qs[1:])
+        if dump and rank == 0:
+            last = (steps - 1) % len(qs)        # the ring the last timed step ran over
+            dump_outputs(dump, key, dbs[last * ring:(last + 1) * ring])
+        kern_ms = kern_b2b = kern_iso = floor_ms = timing = None
+        if full:
+            kk = max(16, 4 * len(qs))
+            kern_b2b = median_of(lambda: qs[0].time(kk, qs[1:], kernels=False)[0] / kk)
+            kern_ms, timing = kernel_duration(lambda: qs[0].time_dispatch(kk, qs[1:]), kern_b2b)
+            _, kern_iso = qs[0].time(min(kk, 32), qs[1:])
         for q in qs:
             q.destroy()
         frames_per_step, ab_step = batch * ring, ab * ring
@@ -389,16 +433,20 @@ def measure(ctx, dist, key, steps, warmup, rank):
         wall = time.perf_counter() - t0     # this rank's region; the max over ranks below
         dist.barrier()
         wall_max = dist.max(wall)
-        # roofline: the kernel's own duration over 500 back-to-back launches on
-        # ONE stream, each launch stamped by its dispatch (hipExtLaunchKernel: the
-        # figure rocprofv3's kernel trace reports), median of 5 such runs; kept
-        # beside it: events around the 500 launches (dispatch gaps included) and
-        # around each single launch (dispatch included)
-        kk = 500
-        kern_b2b = median_of(lambda: ctx.time_dev_streams(dbs, kk, 1) / kk)
-        kern_ms, timing = kernel_duration(lambda: ctx.time_op_dispatch(mosrx.OP_CLASSIFY, dbs, kk), kern_b2b)
-        kern_iso = ctx.time_dev_kernels(dbs, kk)
-        floor_ms = stamp_floor(ctx, dbs[0], kk, timing)
+        if dump and rank == 0:
+            dump_outputs(dump, key, [dbs[(steps - 1) % len(dbs)]])     # the last timed step's batch
+        kern_ms = kern_b2b = kern_iso = floor_ms = timing = None
+        if full:
+            # roofline: the kernel's own duration over 500 back-to-back launches on
+            # ONE stream, each launch stamped by its dispatch (hipExtLaunchKernel: the
+            # figure rocprofv3's kernel trace reports), median of 5 such runs; kept
+            # beside it: events around the 500 launches (dispatch gaps included) and
+            # around each single launch (dispatch included)
+            kk = 500
+            kern_b2b = median_of(lambda: ctx.time_dev_streams(dbs, kk, 1) / kk)
+            kern_ms, timing = kernel_duration(lambda: ctx.time_op_dispatch(mosrx.OP_CLASSIFY, dbs, kk), kern_b2b)
+            kern_iso = ctx.time_dev_kernels(dbs, kk)
+            floor_ms = stamp_floor(ctx, dbs[0], kk, timing)
         frames_per_step, ab_step = batch, ab
         method = f"one launch per batch, batch i on stream i % {STREAMS}"
     for d in dbs:
@@ -426,6 +474,8 @@ def measure(ctx, dist, key, steps, warmup, rank):
         "kernel_ms_isolated": kern_iso,
         "per_rank_device_gbps": {"min": round(min(per_rank), 1), "max": round(max(per_rank), 1)},
     }
+    if not full:
+        return out, tr
     achieved = ab_step / (kern_ms * 1e-3) / 1e9
     pmc = load_pmc(key)
     out["roofline"] = {
@@ -1093,8 +1143,15 @@ def main():
                     help="batches in flight for the one-launch-per-batch rows (1 = strictly serial launches)")
     ap.add_argument("--no-hint", action="store_true",
                     help="hand the resident batches over without their layout hint (A/B of MOSRX_BATCH_UNIFORM)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (PCIe) and backend legs")
+    ap.add_argument("--full", action="store_true",
+                    help="every row of --workloads, the roofline's kernel durations, the read probe, the CPU "
+                         "baselines, the end-to-end and backend legs, and the detail record (a plain run: the "
+                         "headline workload's timed steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the headline workload's last timed step computed (its records, one "
+                         "<field>.npy each, float32 / float64) into DIR")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end (PCIe) and backend legs")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="where the full record (every row and leg) is written")
     args = ap.parse_args()
@@ -1116,16 +1173,22 @@ def main():
     numa = mosrx.bind_to_gpu_node(device)
     ctx = mosrx.Context(device)
     keys = [k for k in args.workloads.split(",") if k]
+    head = "M1500" if "M1500" in keys else keys[0]
+    if args.dump_outputs and head in OPS:
+        ap.error(f"--dump-outputs: the headline workload must be a classify row, not {head}")
+    if not args.full:
+        keys = [head]       # a plain run: the headline figure's workload alone
     results, traces = {}, {}
     for k in keys:
-        results[k], traces[k] = measure(ctx, dist, k, args.steps, args.warmup, rank)
+        results[k], traces[k] = measure(ctx, dist, k, args.steps, args.warmup, rank, full=args.full,
+                                        dump=args.dump_outputs if k == head else None)
         if rank == 0:
             r = results[k]
-            print(f"[bench] {k}: {r['gbps']:.1f} GB/s {r['mpkts']:.1f} Mpkts/s "
-                  f"kernel {r['kernel_ms']*1e3:.1f} us roofline {r['roofline']['frac']:.3f}",
+            print(f"[bench] {k}: {r['gbps']:.1f} GB/s {r['mpkts']:.1f} Mpkts/s" + (
+                  f" kernel {r['kernel_ms']*1e3:.1f} us roofline {r['roofline']['frac']:.3f}" if args.full else ""),
                   file=sys.stderr, flush=True)
     e2e = None
-    if not args.no_e2e and any(k in traces for k in ("M1500", "S64", "IMIX")):
+    if args.full and not args.no_e2e and any(k in traces for k in ("M1500", "S64", "IMIX")):
         # every leg runs on every rank at once, between barriers (Dist.leg), each rank
         # on its own GPU and host thread; e2e[...] is this rank's figure (rank 0's in
         # the record), e2e["aggregate"][...] the job's: all ranks' frames over the
@@ -1200,8 +1263,7 @@ def main():
     # baselines, with no other rank's timed region in flight, and the others wait
     dist.barrier()
     cpu = None
-    if rank == 0 and not args.no_cpu:
-        head = "M1500" if "M1500" in traces else keys[0]
+    if rank == 0 and args.full and not args.no_cpu:
         cpu = cpu_baseline(traces[head], head, min_s=10.0, ws=ws, host_cpus=host_cpus)
         progress(f"cpu baseline (port): {cpu['value']} GB/s on 1 core, "
                  f"{(cpu.get('per_gpu_share') or {}).get('value')} on one GPU's share")
@@ -1245,7 +1307,7 @@ def main():
         results["FW64"] = measure_fw64(ctx, 2.0)
         progress("config #1 (simple_firewall) legs done")
     read_ceiling = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # the box's streaming-read rate over a >= 1.5 GB working set (no Infinity-
         # Cache hits), with 128 MiB launches (the single-batch rows' size: their ramp
         # and drain included) and 768 MiB launches (the ring rows' size, ~805 MB)
@@ -1256,8 +1318,10 @@ def main():
     dist.close()
     if rank != 0:
         return
-    head = "M1500" if "M1500" in results else keys[0]
     h = results[head]
+    if not args.full:
+        print(json.dumps(plain_line(h, ws, args)), flush=True)
+        return
     detail = {
         "metric": METRIC,
         "value": round(h["gbps"], 2),
@@ -1304,6 +1368,33 @@ def main():
         print(f"[bench] could not write {path}: {e}", file=sys.stderr)
     print("[bench-detail] " + json.dumps(detail), file=sys.stderr, flush=True)
     print(json.dumps(headline_line(detail, h, head, results, e2e)), flush=True)
+
+
+def plain_line(h, ws, args):
+    """A plain run's record: the contract's fields of the headline workload (the
+    same figures, named as in the --full line), and nothing that takes a run of
+    its own."""
+    return {
+        "metric": METRIC,
+        "value": round(h["gbps"], 2),
+        "unit": "GB/s",
+        "mpkts_per_s": round(h["mpkts"], 2),
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(h["ms_per_step"], 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (seeded splitmix64 traces, BASELINE.md §3)",
+        "config": {"workload": h["workload"], "batch": h["batch"], "batches_per_step": h["batches_per_step"],
+                   "algo_bytes_per_batch": h["algo_bytes_per_batch"],
+                   "parallelism": f"replicas x{ws}: the job's batches round-robin per GPU (shard_plan), no collectives"},
+        "per_rank_device_gbps": h["per_rank_device_gbps"],
+        "outputs": args.dump_outputs,
+        "detail": "roofline, other rows, CPU baselines, end-to-end legs: --full",
+    }
 
 
 def _compact_cpu(c):
