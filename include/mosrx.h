@@ -234,6 +234,52 @@ int  mosrx_queue_create_ex(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, void
 int  mosrx_time_queue(mosrx_ctx *c, mosrx_queue *const *q, uint32_t nq, uint32_t iters,
                       float *total_ms, float *avg_kernel_ms);
 
+/* ---- queue steering: the per-core sort a NIC's RSS does ------------------- */
+/* A stable partition of a batch's frame indices by the records' `queue` byte
+ * (GetRSSCPUCore, util.c:114-131), computed on the GPU from the records a
+ * classify call wrote:
+ *   idx[n]                       batch-local frame indices grouped by queue,
+ *                                ascending within a queue (arrival order kept)
+ *   qstart[MOSRX_STEER_QSLOTS]   queue q's frames are idx[qstart[q] .. qstart[q+1]),
+ *                                qstart[256] == n
+ * The slot count does not depend on num_queues (the key is a byte, so no
+ * record value indexes outside qstart): with num_queues = 8, entries 8..256
+ * all equal n.  Each mTCP thread owns the flows whose hash maps to its core
+ * (and api.c:1056 picks source ports to match); this is that map applied to a
+ * batch from a single ingress.  Three kernel launches (histogram, scan,
+ * scatter) behind the classify launch on the same stream. */
+#define MOSRX_STEER_QSLOTS 257
+/* Scratch a steer of n frames needs (no GPU needed; never 0, non-decreasing
+ * in n), and the frames one workgroup takes. */
+size_t   mosrx_steer_scratch_bytes(uint32_t n);
+uint32_t mosrx_steer_tile(void);
+/* Steer one device-resident batch: d_rec are its n records of rec_bytes (16:
+ * mosrx_result, 8: mosrx_result8) as a classify call on the same stream left
+ * them; d_idx[n], d_qstart[MOSRX_STEER_QSLOTS] and d_scratch (4-byte aligned,
+ * at least mosrx_steer_scratch_bytes(n)) are the caller's, so the call
+ * allocates nothing and is graph-capturable.  -EINVAL: rec_bytes not 8 or 16,
+ * a NULL or misaligned pointer, scratch too small.  n == 0 returns 0 and
+ * launches nothing. */
+int  mosrx_steer_dev(mosrx_ctx *c, const void *d_rec, uint32_t n, int rec_bytes, uint32_t *d_idx,
+                     uint32_t *d_qstart, void *d_scratch, size_t scratch_bytes, void *stream);
+/* Attach per-batch steer outputs to a batch queue (d_idx[i]: n_i entries,
+ * NULL allowed for an empty batch; d_qstart[i]: MOSRX_STEER_QSLOTS): every
+ * mosrx_queue_run then enqueues the three steer launches behind the classify
+ * launch on the same stream.  The queue's scratch is allocated at the first
+ * attach.  Both NULL detaches: the queue runs exactly as before.  Not while a
+ * run of the queue is in flight. */
+int  mosrx_queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart);
+/* Arm the next group submit on `slot` (any mosrx_classify_host_group_submit*
+ * variant), once: the steer launches follow the group's classify launch on
+ * the slot's stream, batch i's outputs land in h_idx[i] (n_i entries) and
+ * h_qstart[i] (MOSRX_STEER_QSLOTS) by the rule of the other output arrays --
+ * written in place for a direct group whose outputs (these included) are all
+ * pinned, else copied back with the records.  The two pointer arrays must
+ * stay valid until that submit returns.  The slot's steer buffers are part of
+ * mosrx_classify_host_reserve, so arming never makes a slot grow in traffic.
+ * Both NULL disarms.  -EBUSY while the slot runs. */
+int  mosrx_slot_steer(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned
@@ -388,7 +434,10 @@ int  mosrx_time_dev_kernels(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb,
  * (CLASSIFY_BPF). */
 enum { MOSRX_OP_CLASSIFY = 0, MOSRX_OP_CLASSIFY_FH = 1, MOSRX_OP_BPF = 2, MOSRX_OP_TX_CSUM = 3,
        MOSRX_OP_CLASSIFY_BPF = 4, MOSRX_OP_CLASSIFY_TI = 5 /* aux[i]: mosrx_tcpinfo side arrays */,
-       MOSRX_OP_TX_CHECKS = 6 /* out[i]: mosrx_tx_check records, `arg` the flags */ };
+       MOSRX_OP_TX_CHECKS = 6 /* out[i]: mosrx_tx_check records, `arg` the flags */,
+       MOSRX_OP_STEER = 7 /* the steer sequence over records already made: out[i] the records of batch i,
+                           * aux[i] its idx array, `arg` = rec_bytes (8 or 16); qstart and scratch are the
+                           * timing call's own.  Three launches: -ENOTSUP from mosrx_time_op_dispatch */ };
 int  mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t nb, void *const *out,
                    void *const *aux, uint32_t iters, uint32_t nstreams, float *total_ms, float *avg_kernel_ms);
 /* The kernel's own duration, averaged over `iters` back-to-back launches on

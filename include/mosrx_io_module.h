@@ -86,6 +86,14 @@ typedef struct {
                                      * handed out are classified again with them */
 #define MOSRX_PKT_RX_RESULTS8 0x18  /* argp: const mosrx_result8 ** (whole batch): the records of a batch
                                      * classified in compact form (cfg.compact); RX_RESULTS is -1 for it */
+#define MOSRX_PKT_RX_STEER   0x19   /* argp: mosrx_steer_view * -- the exposed batch's frames sorted into
+                                     * per-core queues (cfg.steer; -1 without it) */
+typedef struct mosrx_steer_view {
+	const uint32_t *idx;         /* n batch-local frame indices grouped by queue, ascending within a queue */
+	const uint32_t *qstart;      /* MOSRX_STEER_QSLOTS: queue q's frames are idx[qstart[q] .. qstart[q+1]) */
+	uint32_t n;
+	uint32_t num_queues;         /* of the netdev's stack state: queues num_queues.. are empty */
+} mosrx_steer_view;
 typedef struct mosrx_rx_state {
 	uint32_t num_msp, num_esp;   /* the stack state of the batch's verdicts */
 	uint32_t gen;                /* the netdev's parameter / filter generation they were made with */
@@ -234,6 +242,11 @@ typedef struct mosrx_gpu_module_cfg {
 	                                                 * MOSRX_DIRECT_DEFAULT_KB */
 	uint32_t      direct_frames;                    /* ... and of at most this many frames (default
 	                                                 * MOSRX_DIRECT_DEFAULT_FRAMES) */
+	int32_t       steer;                            /* 1: every group is also steered on the GPU -- each batch's
+	                                                 * frame indices partitioned by the records' queue
+	                                                 * (GetRSSCPUCore), arrival order kept within a queue
+	                                                 * (dev_ioctl(MOSRX_PKT_RX_STEER), mosrx_rx_loop_queues);
+	                                                 * a lone batch then takes the group path.  Default 0 */
 } mosrx_gpu_module_cfg;
 #define MOSRX_GROUP_AUTO        0
 #define MOSRX_DIRECT_DEFAULT_FRAMES 0xFFFFFFFFu   /* no frame limit: a 16K limit made the 64 B 90 % points
@@ -350,6 +363,19 @@ typedef struct mosrx_rx_loop_opts {
 } mosrx_rx_loop_opts;
 int mosrx_rx_loop_ex(const io_module_func *iom, struct mtcp_thread_context *ctx, int nif,
                      const mosrx_rx_loop_opts *opts, mosrx_pkt_fn fn, void *arg, mosrx_rx_stats *st);
+
+/* The loop over a steering backend (cfg.steer), one consumer per mTCP core:
+ * per exposed batch it walks queue 0, then queue 1, ... up to queue nq - 1 in
+ * the order of MOSRX_PKT_RX_STEER's idx (a queue's frames in arrival order)
+ * and calls fn(arg[q], ...) for the frames of queue q; `index` is the frame's
+ * index in the batch.  Frames of queues >= nq (none when nq is the stack's
+ * num_queues) are counted in the stats and handed to nobody.  Rounds as
+ * mosrx_rx_loop: it ends at the first idle round, or after `max_rounds`
+ * rounds (0: no limit).  -ENOTSUP when the backend does not steer.  The hub
+ * that hands each queue's frames to another thread's recv_pkts is not here:
+ * DESIGN.md §7. */
+int mosrx_rx_loop_queues(const io_module_func *iom, struct mtcp_thread_context *ctx, int nif, uint32_t nq,
+                         mosrx_pkt_fn fn, void *const *arg, uint64_t max_rounds, mosrx_rx_stats *st);
 
 /* A consumer for mosrx_rx_loop*: the frames mOS forwards with `forward` set,
  * decided from the verdict reason and the stack state as ProcessPacket's paths

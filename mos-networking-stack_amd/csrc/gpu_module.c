@@ -73,6 +73,8 @@ struct stage {
 	mosrx_tcpinfo *ti;        /* pinned, pkt_info TCP fields (cfg.tcpinfo) */
 	uint32_t *match;          /* pinned, BPF match masks (a filter set installed) */
 	uint32_t *fh;             /* pinned, flow-table hashes (cfg.flowhash) */
+	uint32_t *sidx, *sqs;     /* pinned, queue steering (cfg.steer): n indices, MOSRX_STEER_QSLOTS starts */
+	int steered;              /* its last launch filled them (MOSRX_PKT_RX_STEER) */
 	uint32_t n, max_len;
 	uint32_t rec0;            /* its first record's index in the group's record arrays */
 	uint32_t stride;          /* frame i at off[0] + i * stride (a fixed-size packing), else 0: the layout hint */
@@ -98,6 +100,7 @@ struct group {
 	mosrx_tcpinfo *ti;
 	uint32_t *match;
 	uint32_t *fh;
+	uint32_t *sidx, *sqs;     /* cfg.steer: rec_cap indices, cap_st x MOSRX_STEER_QSLOTS queue starts */
 	uint64_t rec_cap;         /* frames the record arrays hold */
 	struct stage *st;         /* cap_st stages */
 	uint32_t cap_st;
@@ -412,6 +415,8 @@ static void group_free(mosrx_ctx *mc, struct group *g)
 	if (g->ti) mosrx_host_free(mc, g->ti);
 	if (g->match) mosrx_host_free(mc, g->match);
 	if (g->fh) mosrx_host_free(mc, g->fh);
+	if (g->sidx) mosrx_host_free(mc, g->sidx);
+	if (g->sqs) mosrx_host_free(mc, g->sqs);
 	free(g->st);
 	memset(g, 0, sizeof(*g));
 }
@@ -481,7 +486,9 @@ static int group_alloc_sized(mosrx_ctx *mc, struct group *g, uint64_t bytes)
 	    mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_result), (void **)&g->res) ||
 	    (g_cfg.tcpinfo && mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_tcpinfo), (void **)&g->ti)) ||
 	    (MATCH_UP_FRONT && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->match)) ||
-	    (g_cfg.flowhash && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->fh)))
+	    (g_cfg.flowhash && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->fh)) ||
+	    (g_cfg.steer && (mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sidx) ||
+	                     mosrx_host_alloc(mc, (size_t)g->cap_st * MOSRX_STEER_QSLOTS * 4, (void **)&g->sqs))))
 		return -ENOMEM;
 	return 0;
 }
@@ -719,6 +726,9 @@ static void group_fill(struct if_state *is, struct group *g)
 		s->ti = g->ti ? g->ti + recs : NULL;
 		s->match = g->match ? g->match + recs : NULL;
 		s->fh = g->fh ? g->fh + recs : NULL;
+		s->sidx = g->sidx ? g->sidx + recs : NULL;
+		s->sqs = g->sqs ? g->sqs + (size_t)i * MOSRX_STEER_QSLOTS : NULL;
+		s->steered = 0;
 		if (!s->n)
 			break;
 		g->nst++;
@@ -795,7 +805,9 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	mosrx_result8 *out8[MOSRX_MAX_GROUP];
 	mosrx_tcpinfo *ti[MOSRX_MAX_GROUP];
 	uint32_t *fh[MOSRX_MAX_GROUP], *mt[MOSRX_MAX_GROUP];
+	uint32_t *sx[MOSRX_MAX_GROUP], *sq[MOSRX_MAX_GROUP];
 	uint32_t i, nb = g->nst - first;
+	int rc;
 	if (follow_mos_state(pv, is))
 		return -1;
 	const int compact = g_cfg.compact;
@@ -809,6 +821,9 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 		ti[i - first] = s->ti;
 		fh[i - first] = s->fh;
 		mt[i - first] = s->match;
+		sx[i - first] = s->sidx;
+		sq[i - first] = s->sqs;
+		s->steered = g_cfg.steer && s->sidx && s->sqs;
 		s->msp = is->params.num_msp;
 		s->esp = is->params.num_esp;
 		s->gen = is->gen;
@@ -817,19 +832,28 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 		s->has_ti = s->ti != NULL && !is->nprog;
 		s->compact = compact;
 	}
+	/* cfg.steer: every group is armed (the submit below takes the arm; sx / sq
+	 * are read before it returns) */
+	if (g_cfg.steer && mosrx_slot_steer(is->mc, k, sx, sq))
+		return -1;
 	if (compact && is->nprog)   /* 8-byte records + the set's masks: the fused kernel's 8-byte form */
-		return mosrx_classify_host_group_submit_bpf_c8(is->mc, k, b, nb, out8, g_cfg.flowhash ? fh : NULL, mt);
-	if (compact)
-		return mosrx_classify_host_group_submit_c8(is->mc, k, b, nb, out8, g_cfg.flowhash ? fh : NULL);
-	if (is->nprog)
-		return mosrx_classify_host_group_submit_bpf(is->mc, k, b, nb, out, g_cfg.flowhash ? fh : NULL, mt);
+		rc = mosrx_classify_host_group_submit_bpf_c8(is->mc, k, b, nb, out8, g_cfg.flowhash ? fh : NULL, mt);
+	else if (compact)
+		rc = mosrx_classify_host_group_submit_c8(is->mc, k, b, nb, out8, g_cfg.flowhash ? fh : NULL);
+	else if (is->nprog)
+		rc = mosrx_classify_host_group_submit_bpf(is->mc, k, b, nb, out, g_cfg.flowhash ? fh : NULL, mt);
 	/* one batch, no copy-free groups: the single-batch submit (no batch table:
 	 * the kernel takes the batch as arguments); with cfg.direct_kb a lone batch
-	 * takes the group path, which can run it with no copies */
-	if (nb == 1 && !g_cfg.flowhash && !g_cfg.direct_kb)
-		return mosrx_classify_host_submit_ex(is->mc, k, &b[0], out[0], ti[0]);
-	return mosrx_classify_host_group_submit_ex(is->mc, k, b, nb, out, g_cfg.tcpinfo ? ti : NULL,
-	                                           g_cfg.flowhash ? fh : NULL);
+	 * takes the group path, which can run it with no copies (and with cfg.steer,
+	 * since the group submits are the steered ones) */
+	else if (nb == 1 && !g_cfg.flowhash && !g_cfg.direct_kb && !g_cfg.steer)
+		rc = mosrx_classify_host_submit_ex(is->mc, k, &b[0], out[0], ti[0]);
+	else
+		rc = mosrx_classify_host_group_submit_ex(is->mc, k, b, nb, out, g_cfg.tcpinfo ? ti : NULL,
+		                                         g_cfg.flowhash ? fh : NULL);
+	if (rc && g_cfg.steer)   /* a submit refused before it took the arm: sx / sq end with this call */
+		mosrx_slot_steer(is->mc, k, NULL, NULL);
+	return rc;
 }
 
 static int group_wait(struct gpu_priv *pv, struct if_state *is, int k, int count)
@@ -1165,6 +1189,16 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 			return -1;
 		*(const uint32_t **)argp = s->fh;
 		return 0;
+	case MOSRX_PKT_RX_STEER: {
+		mosrx_steer_view *v = argp;
+		if (!g_cfg.steer || !s || !s->steered)
+			return -1;
+		v->idx = s->sidx;
+		v->qstart = s->sqs;
+		v->n = s->n;
+		v->num_queues = (uint32_t)pv->ifs[nif].params.num_queues;
+		return 0;
+	}
 	case MOSRX_PKT_RX_TCPINFO:
 		if (!s || !s->has_ti)
 			return -1;

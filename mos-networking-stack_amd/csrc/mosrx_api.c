@@ -200,6 +200,10 @@ int mosrx_open(int device, const mosrx_params *p, mosrx_ctx **out)
 		    hipMalloc((void **)&c->slot[i].d_qdesc, MOSRX_MAX_GROUP * sizeof(mosrx_qdesc)) != hipSuccess ||
 		    hipHostMalloc((void **)&c->slot[i].h_qdesc, MOSRX_MAX_GROUP * sizeof(mosrx_qdesc),
 		                  hipHostMallocDefault) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_sdesc, MOSRX_MAX_GROUP * sizeof(mosrx_sdesc)) != hipSuccess ||
+		    hipHostMalloc((void **)&c->slot[i].h_sdesc, MOSRX_MAX_GROUP * sizeof(mosrx_sdesc),
+		                  hipHostMallocDefault) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_sqstart, (size_t)MOSRX_MAX_GROUP * MOSRX_STEER_QSLOTS * 4) != hipSuccess ||
 		    hipMalloc((void **)&c->slot[i].d_cnt, MOSRX_CNT_WORDS * 4) != hipSuccess ||
 		    hipHostMalloc((void **)&c->slot[i].h_cnt, MOSRX_CNT_WORDS * 4, hipHostMallocDefault) != hipSuccess ||
 		    !(c->slot[i].h_prev = calloc(MOSRX_CNT_WORDS, 4))) {
@@ -230,6 +234,9 @@ static void slot_free(struct slot *s)
 	if (s->d_fh) hipFree(s->d_fh);
 	if (s->d_ti) hipFree(s->d_ti);
 	if (s->d_match) hipFree(s->d_match);
+	if (s->d_sidx) hipFree(s->d_sidx);
+	if (s->d_shist) hipFree(s->d_shist);
+	s->d_sidx = NULL; s->d_shist = NULL;
 	s->d_frames = NULL; s->d_off = NULL; s->d_len = NULL; s->d_res = NULL; s->d_fh = NULL; s->d_ti = NULL;
 	s->d_match = NULL;
 	s->cap_frames = 0; s->cap_n = 0;
@@ -260,6 +267,9 @@ void mosrx_close(mosrx_ctx *c)
 		if (c->slot[i].kev1) hipEventDestroy(c->slot[i].kev1);
 		if (c->slot[i].d_qdesc) hipFree(c->slot[i].d_qdesc);
 		if (c->slot[i].h_qdesc) hipHostFree(c->slot[i].h_qdesc);
+		if (c->slot[i].d_sdesc) hipFree(c->slot[i].d_sdesc);
+		if (c->slot[i].h_sdesc) hipHostFree(c->slot[i].h_sdesc);
+		if (c->slot[i].d_sqstart) hipFree(c->slot[i].d_sqstart);
 		if (c->slot[i].d_cnt) hipFree(c->slot[i].d_cnt);
 		if (c->slot[i].h_cnt) hipHostFree(c->slot[i].h_cnt);
 		free(c->slot[i].h_prev);
@@ -268,6 +278,7 @@ void mosrx_close(mosrx_ctx *c)
 	}
 	mosrx__bpf_jit_free(c);   /* (joins the compile thread; launches drained above) */
 	if (c->d_tables) hipFree(c->d_tables);
+	if (c->steer_tmp) hipFree(c->steer_tmp);
 	for (i = 0; i < MOSRX_BPF_POOL; i++)
 		if (c->d_bpf_pool[i])
 			hipFree(c->d_bpf_pool[i]);
@@ -609,6 +620,13 @@ static uint64_t batch_span(const mosrx_batch *b, const uint8_t **lo_out)
 	return (uint64_t)(hi - lo);
 }
 
+/* Histogram rows a group of n frames can need: every batch's tile count is
+ * rounded up, and a group has at most MOSRX_MAX_GROUP batches. */
+static size_t steer_group_scratch(uint32_t n)
+{
+	return ((size_t)n / MOSRX_STEER_TILE + MOSRX_MAX_GROUP + 1) * MOSRX_STEER_BINS * 4;
+}
+
 int mosrx__slot_reserve(mosrx_ctx *c, struct slot *s, uint64_t frames_bytes, uint32_t n)
 {
 	if (frames_bytes > s->cap_frames || n > s->cap_n) {
@@ -623,7 +641,9 @@ int mosrx__slot_reserve(mosrx_ctx *c, struct slot *s, uint64_t frames_bytes, uin
 		    hipMalloc((void **)&s->d_res, (size_t)nn * sizeof(mosrx_result)) != hipSuccess ||
 		    hipMalloc((void **)&s->d_fh, (size_t)nn * 4) != hipSuccess ||
 		    hipMalloc((void **)&s->d_ti, (size_t)nn * sizeof(mosrx_tcpinfo)) != hipSuccess ||
-		    hipMalloc((void **)&s->d_match, (size_t)nn * 4) != hipSuccess) {
+		    hipMalloc((void **)&s->d_match, (size_t)nn * 4) != hipSuccess ||
+		    hipMalloc((void **)&s->d_sidx, (size_t)nn * 4) != hipSuccess ||
+		    hipMalloc((void **)&s->d_shist, steer_group_scratch(nn)) != hipSuccess) {
 			slot_free(s);
 			return -ENOMEM;
 		}
@@ -1002,6 +1022,72 @@ static int direct_outputs(int device, const mosrx_batch *b, uint32_t nb, mosrx_r
 	return 1;
 }
 
+/* The same for an armed group's steer outputs (mosrx_slot_steer): their device
+ * addresses go into the slot's steer table sd[]. */
+static int steer_outputs(int device, const mosrx_batch *b, uint32_t nb, uint32_t *const *h_idx,
+                         uint32_t *const *h_qstart, mosrx_sdesc *sd)
+{
+	uint32_t i;
+	for (i = 0; i < nb; i++) {
+		sd[i].idx = sd[i].qstart = NULL;
+		if (!b[i].n)
+			continue;
+		if (!(sd[i].idx = mosrx__host_dev_of(h_idx[i], (uint64_t)b[i].n * 4, device)) ||
+		    !(sd[i].qstart = mosrx__host_dev_of(h_qstart[i], MOSRX_STEER_QSLOTS * 4, device)))
+			return 0;
+	}
+	return 1;
+}
+
+/* The steer launches of an armed group, behind its classify launch on the
+ * slot's stream: over the records where that launch wrote them (s->h_qdesc),
+ * into the caller's pinned arrays (in_place: steer_outputs filled the table)
+ * or the slot's buffers, which are then copied back -- one copy per run of
+ * batches whose host arrays follow each other. */
+static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
+                       uint32_t *const *h_idx, uint32_t *const *h_qstart)
+{
+	mosrx_sparams sp;
+	uint32_t i, tiles = 0;
+	uint64_t pre = 0;
+	int rc;
+	memset(&sp, 0, sizeof(sp));
+	for (i = 0; i < nb; pre += b[i].n, i++) {
+		mosrx_sdesc *d = &s->h_sdesc[i];
+		if (!in_place) {
+			d->idx = b[i].n ? s->d_sidx + pre : NULL;
+			d->qstart = b[i].n ? s->d_sqstart + (size_t)i * MOSRX_STEER_QSLOTS : NULL;
+		}
+		d->rec = (const uint8_t *)s->h_qdesc[i].out;
+		d->n = b[i].n;
+		d->tile_base = tiles;
+		tiles += (b[i].n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
+	}
+	HIPCHK(hipMemcpyAsync(s->d_sdesc, s->h_sdesc, nb * sizeof(mosrx_sdesc), hipMemcpyHostToDevice, s->stream));
+	sp.desc = s->d_sdesc;
+	sp.hist = s->d_shist;
+	sp.nb = nb;
+	sp.rec_bytes = (uint32_t)rsz;
+	sp.total_tiles = tiles;
+	if ((rc = mosrx_launch_steer(&sp, s->stream)))
+		return rc;
+	for (i = 0, pre = 0; !in_place && i < nb;) {
+		uint32_t j = i + 1;
+		uint64_t n = b[i].n;
+		while (b[i].n && j < nb && b[j].n && h_idx[j] == h_idx[j - 1] + b[j - 1].n &&
+		       h_qstart[j] == h_qstart[j - 1] + MOSRX_STEER_QSLOTS)
+			n += b[j++].n;
+		if (n) {
+			HIPCHK(hipMemcpyAsync(h_idx[i], s->d_sidx + pre, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
+			HIPCHK(hipMemcpyAsync(h_qstart[i], s->d_sqstart + (size_t)i * MOSRX_STEER_QSLOTS,
+			                      (size_t)(j - i) * MOSRX_STEER_QSLOTS * 4, hipMemcpyDeviceToHost, s->stream));
+		}
+		pre += n;
+		i = j;
+	}
+	return 0;
+}
+
 int mosrx_classify_host_group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t nb,
                                      mosrx_result *const *h_out, mosrx_tcpinfo *const *h_tcpinfo)
 {
@@ -1026,17 +1112,23 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	struct out_dev od[MOSRX_MAX_GROUP];
 	int rc, unknown = 0, kind, tpb_ok = 1;
 	int fused = 0, uni = 0, direct, out_direct;
+	uint32_t *const *h_sidx, *const *h_sqs;
 	if (!c || slot < 0 || slot >= NSLOT || !b || !h_out || nb == 0 || nb > MOSRX_MAX_GROUP ||
 	    (h_match && h_tcpinfo) || (compact && h_tcpinfo))
 		return -EINVAL;
 	s = &c->slot[slot];
 	if (s->busy)
 		return -EBUSY;
+	/* mosrx_slot_steer armed this submit, whatever becomes of it */
+	h_sidx = s->steer_idx;
+	h_sqs = s->steer_qstart;
+	s->steer_idx = s->steer_qstart = NULL;
 	for (i = 0; i < nb; i++) {
 		if ((rc = mosrx__check_batch(&b[i], 0)))
 			return rc;
 		if (b[i].n && (!h_out[i] || (h_tcpinfo && !h_tcpinfo[i]) || (h_fhash && !h_fhash[i]) ||
-		               (h_match && !h_match[i])))
+		               (h_match && !h_match[i]) ||
+		               (h_sidx && (!h_sidx[i] || !h_sqs[i] || (((uintptr_t)h_sidx[i] | (uintptr_t)h_sqs[i]) & 3)))))
 			return -EINVAL;
 		if (!b[i].max_len)
 			unknown = 1;
@@ -1058,15 +1150,16 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	}
 	HIPCHK(hipSetDevice(c->device));
 	direct = direct_regions(c, s, r, nr, ntot, &dev_bytes);
-	out_direct = direct && direct_outputs(c->device, b, nb, h_out, rsz, h_tcpinfo, h_fhash, h_match, od);
+	out_direct = direct && direct_outputs(c->device, b, nb, h_out, rsz, h_tcpinfo, h_fhash, h_match, od) &&
+	             (!h_sidx || steer_outputs(c->device, b, nb, h_sidx, h_sqs, s->h_sdesc));
 	if (!direct) {
 		group_copy(s, r, nr, &dev_bytes, 0);
 		if ((rc = mosrx__slot_reserve(c, s, dev_bytes, ntot)))
 			return rc;
 		if ((rc = group_copy(s, r, nr, &dev_bytes, 1)))
 			return rc;
-	} else if (!out_direct && (rc = mosrx__slot_reserve(c, s, 0, ntot))) {
-		return rc;
+	} else if ((!out_direct || h_sidx) && (rc = mosrx__slot_reserve(c, s, 0, ntot))) {
+		return rc;   /* (a steered group's histogram rows are the slot's even when every output is written in place) */
 	}
 	kind = kind_of(c, unknown ? 0 : maxl, dev_bytes, ntot);   /* one shape for the whole group */
 	tile = MOSRX_KIND_FRAMES(kind);
@@ -1147,6 +1240,8 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	if (c->timing && h_match && !fused)
 		HIPCHK(hipEventRecord(s->kev1, s->stream));
 	s->timed = c->timing;
+	if (h_sidx && (rc = group_steer(s, b, nb, rsz, out_direct, h_sidx, h_sqs)))
+		return rc;
 	/* results: one copy when the host buffers follow each other, else per batch */
 	for (i = 0, pre = 0; !out_direct && i < nb;) {
 		uint32_t j = i + 1;
@@ -1537,6 +1632,32 @@ int mosrx_time_host(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, mosrx_resul
 	return 0;
 }
 
+/* MOSRX_OP_STEER's qstart + scratch: one block for the context stream and one
+ * per timing stream, each qstart (rounded to STEER_TMP_QS bytes) followed by
+ * the scratch of the largest batch. */
+#define STEER_TMP_QS ((MOSRX_STEER_QSLOTS * 4 + 255) & ~255)
+static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
+{
+	uint32_t i, maxn = 0;
+	size_t stride, bytes;
+	for (i = 0; i < nb; i++)
+		maxn = b[i].n > maxn ? b[i].n : maxn;
+	stride = STEER_TMP_QS + ((mosrx_steer_scratch_bytes(maxn) + 255) & ~(size_t)255);
+	bytes = stride * (MOSRX_MAX_STREAMS + 1);
+	if (bytes > c->steer_tmp_bytes) {
+		HIPCHK(hipDeviceSynchronize());
+		if (c->steer_tmp)
+			hipFree(c->steer_tmp);
+		c->steer_tmp = NULL;
+		c->steer_tmp_bytes = 0;
+		if (hipMalloc((void **)&c->steer_tmp, bytes) != hipSuccess)
+			return -ENOMEM;
+		c->steer_tmp_bytes = bytes;
+	}
+	c->steer_tmp_stride = stride;
+	return 0;
+}
+
 /* One enqueue of operation `op` on batch b (see mosrx_time_op). */
 static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out, void *aux, hipStream_t s)
 {
@@ -1548,6 +1669,17 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 	case MOSRX_OP_CLASSIFY_BPF: return mosrx_classify_bpf_dev(c, b, (mosrx_result *)out, (uint32_t *)aux, s);
 	case MOSRX_OP_CLASSIFY_TI: return mosrx_classify_dev_ex(c, b, (mosrx_result *)out, NULL, (mosrx_tcpinfo *)aux, s);
 	case MOSRX_OP_TX_CHECKS: return mosrx_tx_csum_dev_checks(c, b, arg, (mosrx_tx_check *)out, s);
+	case MOSRX_OP_STEER: {
+		/* the stream's own qstart + scratch block (steer_tmp_reserve): launches on
+		 * different streams overlap */
+		uint32_t k = 0;
+		uint8_t *blk;
+		while (k < c->nxs && c->xs[k] != s)
+			k++;
+		blk = c->steer_tmp + (size_t)(k < c->nxs ? k + 1 : 0) * c->steer_tmp_stride;
+		return mosrx_steer_dev(c, out, b->n, arg, (uint32_t *)aux, (uint32_t *)blk, blk + STEER_TMP_QS,
+		                       c->steer_tmp_stride - STEER_TMP_QS, s);
+	}
 	default: return -EINVAL;
 	}
 }
@@ -1634,10 +1766,14 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 {
 	int rc;
 	if (!c || !b || nb == 0 || iters == 0 || nstreams == 0 || nstreams > MOSRX_MAX_STREAMS ||
-	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_TX_CHECKS || (op != MOSRX_OP_TX_CSUM && !out) ||
-	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI) && !aux))
+	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER || (op != MOSRX_OP_TX_CSUM && !out) ||
+	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI ||
+	      op == MOSRX_OP_STEER) && !aux) ||
+	    (op == MOSRX_OP_STEER && arg != 8 && arg != 16))
 		return -EINVAL;
 	HIPCHK(hipSetDevice(c->device));
+	if (op == MOSRX_OP_STEER && (rc = steer_tmp_reserve(c, b, nb)))
+		return rc;
 	if (total_ms && (rc = time_streams(c, op, arg, b, nb, out, aux, iters, nstreams, total_ms)))
 		return rc;
 	if (avg_kernel_ms && (rc = time_kernels(c, op, arg, b, nb, out, aux, iters, avg_kernel_ms)))
@@ -1700,10 +1836,13 @@ int mosrx_time_op_dispatch(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, 
                            void *const *aux, uint32_t iters, float *avg_ms)
 {
 	struct op_run r = {op, arg, b, nb, out, aux};
-	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_TX_CHECKS ||
+	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER ||
 	    (op != MOSRX_OP_TX_CSUM && !out) ||
-	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI) && !aux))
+	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI ||
+	      op == MOSRX_OP_STEER) && !aux))
 		return -EINVAL;
+	if (op == MOSRX_OP_STEER)   /* three launches: no single dispatch to stamp */
+		return -ENOTSUP;
 	/* (the BPF ops are one launch with the fused kernel / the set's own kernel;
 	 * classify + the set's kernel, two, is refused by the launch count) */
 	HIPCHK(hipSetDevice(c->device));
@@ -1826,6 +1965,12 @@ struct mosrx_queue {
 	int uni;             /* some batch carries a layout hint */
 	int match;           /* the descriptors' bmatch: the installed BPF set's masks */
 	uint32_t **d_match;  /* per batch (the non-fused form) */
+	/* queue steering (mosrx_queue_set_steer): the batches' steer table and the
+	 * histogram rows, allocated at the first attach; steer: outputs attached */
+	mosrx_sdesc *d_sdesc;
+	uint32_t *d_shist;
+	uint32_t steer_tiles;
+	int steer;
 };
 
 int mosrx_queue_create_ex(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, void *const *d_out,
@@ -1914,7 +2059,7 @@ int mosrx_queue_create(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, mosrx_re
 	return mosrx_queue_create_ex(c, b, nb, (void *const *)d_out, NULL, NULL, 0, q);
 }
 
-int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
+static int queue_classify(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 {
 	mosrx_qparams qp;
 	const hipStream_t s = stream ? (hipStream_t)stream : c ? c->stream : NULL;
@@ -1945,6 +2090,102 @@ int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 	return 0;
 }
 
+int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
+{
+	mosrx_sparams sp;
+	int rc = queue_classify(c, q, stream);
+	if (rc || !q->steer)
+		return rc;
+	memset(&sp, 0, sizeof(sp));
+	sp.desc = q->d_sdesc;
+	sp.hist = q->d_shist;
+	sp.nb = q->nb;
+	sp.rec_bytes = q->compact ? 8u : 16u;
+	sp.total_tiles = q->steer_tiles;
+	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
+}
+
+int mosrx_queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart)
+{
+	mosrx_sdesc *h;
+	uint32_t i, tiles = 0;
+	if (!c || !q || !d_idx != !d_qstart)
+		return -EINVAL;
+	if (!d_idx) {
+		q->steer = 0;
+		return 0;
+	}
+	for (i = 0; i < q->nb; i++)
+		if (q->h_desc[i].n && (!d_idx[i] || !d_qstart[i] || (((uintptr_t)d_idx[i] | (uintptr_t)d_qstart[i]) & 3)))
+			return -EINVAL;
+	if (!(h = calloc(q->nb, sizeof(*h))))
+		return -ENOMEM;
+	for (i = 0; i < q->nb; i++) {
+		h[i].rec = (const uint8_t *)q->h_desc[i].out;
+		h[i].n = q->h_desc[i].n;
+		h[i].idx = h[i].n ? d_idx[i] : NULL;
+		h[i].qstart = h[i].n ? d_qstart[i] : NULL;
+		h[i].tile_base = tiles;
+		tiles += (h[i].n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
+	}
+	q->steer = 0;
+	if (hipSetDevice(c->device) != hipSuccess ||
+	    (!q->d_sdesc && hipMalloc((void **)&q->d_sdesc, (size_t)q->nb * sizeof(*h)) != hipSuccess) ||
+	    (!q->d_shist && hipMalloc((void **)&q->d_shist, ((size_t)tiles + 1) * MOSRX_STEER_BINS * 4) != hipSuccess)) {
+		free(h);
+		return -ENOMEM;
+	}
+	if (hipMemcpy(q->d_sdesc, h, (size_t)q->nb * sizeof(*h), hipMemcpyHostToDevice) != hipSuccess) {
+		free(h);
+		return -EIO;
+	}
+	free(h);
+	q->steer_tiles = tiles;
+	q->steer = 1;
+	return 0;
+}
+
+int mosrx_slot_steer(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart)
+{
+	if (!c || slot < 0 || slot >= NSLOT || !h_idx != !h_qstart)
+		return -EINVAL;
+	if (c->slot[slot].busy)
+		return -EBUSY;
+	c->slot[slot].steer_idx = h_idx;
+	c->slot[slot].steer_qstart = h_qstart;
+	return 0;
+}
+
+size_t mosrx_steer_scratch_bytes(uint32_t n)
+{
+	const size_t tiles = ((size_t)n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
+	return (tiles ? tiles : 1) * MOSRX_STEER_BINS * 4;
+}
+
+uint32_t mosrx_steer_tile(void) { return MOSRX_STEER_TILE; }
+
+int mosrx_steer_dev(mosrx_ctx *c, const void *d_rec, uint32_t n, int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart,
+                    void *d_scratch, size_t scratch_bytes, void *stream)
+{
+	mosrx_sparams sp;
+	if (!c || !d_rec || !d_idx || !d_qstart || !d_scratch || (rec_bytes != 8 && rec_bytes != 16) ||
+	    (((uintptr_t)d_rec | (uintptr_t)d_idx | (uintptr_t)d_qstart | (uintptr_t)d_scratch) & 3) ||
+	    scratch_bytes < mosrx_steer_scratch_bytes(n))
+		return -EINVAL;
+	if (n == 0)
+		return 0;
+	memset(&sp, 0, sizeof(sp));
+	sp.one.rec = (const uint8_t *)d_rec;
+	sp.one.idx = d_idx;
+	sp.one.qstart = d_qstart;
+	sp.one.n = n;
+	sp.hist = (uint32_t *)d_scratch;
+	sp.nb = 1;
+	sp.rec_bytes = (uint32_t)rec_bytes;
+	sp.total_tiles = (n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
+	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
+}
+
 void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 {
 	if (!q)
@@ -1953,6 +2194,10 @@ void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 		hipSetDevice(c->device);
 	if (q->d_desc)
 		hipFree(q->d_desc);
+	if (q->d_sdesc)
+		hipFree(q->d_sdesc);
+	if (q->d_shist)
+		hipFree(q->d_shist);
 	free(q->h_desc);
 	free(q->d_match);
 	free(q);

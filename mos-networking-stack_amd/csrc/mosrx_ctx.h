@@ -9,6 +9,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "mosrx_internal.h"
+#include "mosrx_steer.h"
 
 #define HIPCHK(x) do { if ((x) != hipSuccess) return -EIO; } while (0)
 
@@ -61,6 +62,14 @@ struct slot {
 	mosrx_qdesc *d_qdesc;
 	const mosrx_qdesc *hq_dev; /* h_qdesc's device address (a direct group's batch table), NULL: none */
 	int direct;                /* the last group submit was direct (mosrx_set_direct) */
+	/* queue steering of a group (mosrx_slot_steer): the armed outputs (NULL:
+	 * none; taken by the next group submit), the group's batch table (pinned,
+	 * copied to d_sdesc per armed submit), and the buffers slot_reserve sizes
+	 * with the rest: idx for cap_n frames, a histogram row per tile a group of
+	 * cap_n frames in MOSRX_MAX_GROUP batches can have, qstart per batch */
+	uint32_t *const *steer_idx, *const *steer_qstart;
+	mosrx_sdesc *h_sdesc, *d_sdesc;
+	uint32_t *d_sidx, *d_shist, *d_sqstart;
 	int timed;
 	int busy;
 };
@@ -107,6 +116,10 @@ struct mosrx_ctx {
 	uint64_t direct_max;             /* largest direct group, input bytes (mosrx_set_direct); 0: none */
 	uint32_t direct_frames;          /*   and its most frames */
 	float last_kernel_ms;            /* kernel time of the last waited submit, -1 if not timed */
+	/* MOSRX_OP_STEER's own qstart + scratch, one block of steer_tmp_stride bytes
+	 * per timing stream and one for the context stream (mosrx_time_op) */
+	uint8_t *steer_tmp;
+	size_t steer_tmp_stride, steer_tmp_bytes;
 };
 
 int mosrx__check_batch(const mosrx_batch *b, int dev);

@@ -1,0 +1,48 @@
+/*
+ * mosrx_steer.h — shared between the C host library (mosrx_api.c) and the
+ * queue-steering kernels (mosrx_steer.hip).  Plain C layout.  Kept out of
+ * mosrx_internal.h, which is embedded for hipRTC: the fused kernels' source
+ * does not change with it.
+ */
+#ifndef MOSRX_STEER_H
+#define MOSRX_STEER_H
+
+#include "../../include/mosrx.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Frames per workgroup of the histogram and scatter launches: 8 waves, each
+ * taking 4 slices of 64 frames in index order.  One histogram row (256 u32)
+ * per tile: 0.5 B of scratch per frame. */
+#define MOSRX_STEER_TILE    2048u
+#define MOSRX_STEER_BINS    256u
+#define MOSRX_STEER_THREADS 512u
+
+/* One batch to steer (device resident for the multi-batch form), 32 bytes. */
+typedef struct mosrx_sdesc {
+	const uint8_t *rec;       /* n records of rec_bytes each, 4-byte aligned */
+	uint32_t      *idx;       /* n */
+	uint32_t      *qstart;    /* MOSRX_STEER_QSLOTS; NULL only with n == 0: nothing written */
+	uint32_t       n;
+	uint32_t       tile_base; /* the batch's first histogram row = its first workgroup in the launch */
+} mosrx_sdesc;
+
+typedef struct mosrx_sparams {
+	const mosrx_sdesc *desc;  /* nb entries in device-visible memory, or NULL: the one batch in `one` */
+	mosrx_sdesc        one;
+	uint32_t          *hist;  /* total_tiles rows of MOSRX_STEER_BINS u32 */
+	uint32_t           nb;
+	uint32_t           rec_bytes;   /* 8 or 16 */
+	uint32_t           total_tiles;
+} mosrx_sparams;
+
+/* The three launches (histogram, scan, scatter) on `stream` (a hipStream_t);
+ * 0, -EINVAL or -EIO.  Allocates nothing. */
+int mosrx_launch_steer(const mosrx_sparams *sp, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

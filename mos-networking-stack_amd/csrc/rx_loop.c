@@ -132,6 +132,81 @@ int mosrx_rx_loop(const io_module_func *iom, struct mtcp_thread_context *ctx, in
 	return mosrx_rx_loop_ex(iom, ctx, nif, &o, fn, arg, st);
 }
 
+/* The receive loop over a steering backend: each exposed batch is walked queue
+ * by queue in MOSRX_PKT_RX_STEER's order, queue q's frames going to arg[q]
+ * (one consumer per mTCP core, each seeing its flows' frames in arrival
+ * order, as the per-core rx queues of an RSS NIC deliver them). */
+int mosrx_rx_loop_queues(const io_module_func *iom, struct mtcp_thread_context *ctx, int nif, uint32_t nq,
+                         mosrx_pkt_fn fn, void *const *arg, uint64_t max_rounds, mosrx_rx_stats *st)
+{
+	int rx_inf;
+	if (!iom || !iom->recv_pkts || !iom->get_rptr || !st || nif <= 0 || nq == 0 || nq > MOSRX_STEER_QSLOTS - 1 ||
+	    (fn && !arg))
+		return -EINVAL;
+	memset(st, 0, sizeof(*st));
+	for (;;) {
+		int any = 0;
+		st->rounds++;
+		for (rx_inf = 0; rx_inf < nif; rx_inf++) {
+			const mosrx_result *res = NULL;
+			const mosrx_result8 *res8 = NULL;
+			mosrx_steer_view v;
+			mosrx_result one;
+			uint32_t q, k;
+			const int32_t recv_cnt = iom->recv_pkts(ctx, rx_inf);
+			if (recv_cnt < 0) {
+				st->recv_errors++;
+				continue;
+			}
+			if (recv_cnt == 0)
+				continue;
+			any = 1;
+			st->batches++;
+			memset(&v, 0, sizeof(v));
+			if (!iom->dev_ioctl ||
+			    ((iom->dev_ioctl(ctx, rx_inf, MOSRX_PKT_RX_RESULTS, &res) || !res) &&
+			     (iom->dev_ioctl(ctx, rx_inf, MOSRX_PKT_RX_RESULTS8, &res8) || !res8)) ||
+			    iom->dev_ioctl(ctx, rx_inf, MOSRX_PKT_RX_STEER, &v) || !v.idx || !v.qstart)
+				return -ENOTSUP;
+			if (v.n != (uint32_t)recv_cnt || v.qstart[0] != 0 || v.qstart[MOSRX_STEER_QSLOTS - 1] != v.n)
+				return -EIO;
+			memset(&one, 0, sizeof(one));
+			for (q = 0; q < MOSRX_STEER_QSLOTS - 1; q++) {
+				if (v.qstart[q] > v.qstart[q + 1] || v.qstart[q + 1] > v.n)
+					return -EIO;
+				for (k = v.qstart[q]; k < v.qstart[q + 1]; k++) {
+					const uint32_t i = v.idx[k];
+					uint16_t len = 0;
+					const uint8_t *pkt;
+					const mosrx_result *r = res ? &res[i] : &one;
+					if (i >= v.n || !(pkt = iom->get_rptr(ctx, rx_inf, (int)i, &len)))
+						return -EIO;
+					if (!res) {           /* the compact record's fields, zero elsewhere */
+						one.rss = res8[i].rss;
+						one.reason = res8[i].reason;
+						one.queue = res8[i].queue;
+						one.verdict = res8[i].verdict;
+						one.tcp_flags = res8[i].tcp_flags;
+					}
+					st->rx_packets++;
+					st->rx_bytes += (uint64_t)len + ETHER_OVR;
+					if (r->verdict < 0)
+						st->rx_errors++;
+					if (r->reason < MOSRX_R_COUNT)
+						st->by_reason[r->reason]++;
+					if (fn && q < nq)
+						fn(arg[q], rx_inf, (int)i, pkt, len, r);
+				}
+			}
+		}
+		if (iom->send_pkts)               /* core.c:999-1007: flush what the round wrote */
+			for (rx_inf = 0; rx_inf < nif; rx_inf++)
+				iom->send_pkts(ctx, rx_inf);
+		if (!any || (max_rounds && st->rounds >= max_rounds))
+			return 0;
+	}
+}
+
 /* ---- per-frame residency of a paced source (mosrx_rx_loop_opts.probe) ----
  * Frames from a paced source arrive at t0 + k * p and come through the
  * backend in order, so the k-th frame the loop receives is arrival k.  Per

@@ -104,6 +104,8 @@ BPF_INSN = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
 BPF_LEN_FRAME, BPF_LEN_IP = 0, 1
 TX_IP_CSUM, TX_TCP_CSUM = 1 << 4, 1 << 5   # MOS_UPDATE_IP_CHKSUM / MOS_UPDATE_TCP_CHKSUM
 OP_CLASSIFY, OP_CLASSIFY_FH, OP_BPF, OP_TX_CSUM, OP_CLASSIFY_BPF, OP_CLASSIFY_TI, OP_TX_CHECKS = 0, 1, 2, 3, 4, 5, 6
+OP_STEER = 7           # MOSRX_OP_STEER: the steer sequence over a batch's records (arg = rec_bytes)
+STEER_QSLOTS = 257     # MOSRX_STEER_QSLOTS: qstart entries per batch
 # include/mosrx.h mosrx_tx_check: the TX checks of a frame, the frame untouched
 TX_CHECK_DTYPE = np.dtype([("ip_check", "<u2"), ("tcp_check", "<u2"), ("what", "u1"), ("ihl", "u1"),
                            ("pad", "<u2")])
@@ -134,7 +136,12 @@ class ModuleCfg(C.Structure):
                 ("tx_batch", C.c_uint32), ("tcpinfo", C.c_int32), ("group", C.c_uint32),
                 ("group_bytes", C.c_uint64), ("flowhash", C.c_int32), ("tx_csum", C.c_int32),
                 ("numa", C.c_int32), ("compact", C.c_int32), ("group_max_us", C.c_uint32),
-                ("direct_kb", C.c_uint32), ("direct_frames", C.c_uint32)]
+                ("direct_kb", C.c_uint32), ("direct_frames", C.c_uint32), ("steer", C.c_int32)]
+
+
+class SteerView(C.Structure):
+    """mosrx_steer_view (dev_ioctl(MOSRX_PKT_RX_STEER))."""
+    _fields_ = [("idx", C.c_void_p), ("qstart", C.c_void_p), ("n", C.c_uint32), ("num_queues", C.c_uint32)]
 
 
 class ModuleStats(C.Structure):
@@ -339,6 +346,12 @@ def lib():
             "mosrx_gpu_numa_node": (I, [I]),
             "mosrx_numa_pick": (I, [I, C.POINTER(C.c_int), I]),
             "mosrx_topology_set_root": (I, [C.c_char_p]),
+            "mosrx_steer_scratch_bytes": (C.c_size_t, [U32]),
+            "mosrx_steer_tile": (U32, []),
+            "mosrx_steer_dev": (I, [P, P, U32, I, P, P, P, C.c_size_t, P]),
+            "mosrx_queue_set_steer": (I, [P, P, C.POINTER(P), C.POINTER(P)]),
+            "mosrx_slot_steer": (I, [P, I, C.POINTER(P), C.POINTER(P)]),
+            "mosrx_rx_loop_queues": (I, [P, P, I, U32, P, C.POINTER(P), U64, C.POINTER(RxStats)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -524,6 +537,7 @@ class DevBatch:
         self.d_tinfo = None   # allocated on the first classify_dev(..., tcpinfo=True)
         self.d_match = None   # allocated on the first bpf_dev
         self.d_out8 = None    # compact records, allocated on the first classify_dev_compact
+        self.d_sidx = None    # steered frame indices, allocated on the first time_op(OP_STEER)
         self.max_len = int(max_len if max_len is not None else (int(ln.max()) if self.n else 0))
         self.caplen_sum = int(ln.astype(np.uint64).sum())
 
@@ -568,7 +582,7 @@ class DevBatch:
 
     def free(self):
         for b in (self.d_frames, self.d_off, self.d_len, self.d_out, self.d_fhash, self.d_match, self.d_tinfo,
-                  self.d_out8):
+                  self.d_out8, self.d_sidx):
             if b is not None:
                 b.free()
 
@@ -820,6 +834,26 @@ class Context:
         _chk(lib().mosrx_classify_host_group_submit_ex(self.handle, slot, bs, n, o, ti, f),
              "mosrx_classify_host_group_submit_ex")
 
+    def steer_dev(self, d_rec: int, n: int, rec_bytes: int, d_idx: int, d_qstart: int, d_scratch: int,
+                  scratch_bytes: int, sync: bool = True, stream: int | None = None) -> None:
+        """mosrx_steer_dev: the stable partition of a device-resident batch's frame
+        indices by its records' queue byte (device pointers; the caller owns all)."""
+        _chk(lib().mosrx_steer_dev(self.handle, d_rec, n, rec_bytes, d_idx, d_qstart, d_scratch, scratch_bytes,
+                                   stream), "mosrx_steer_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
+    def slot_steer(self, slot: int, idx: list | None, qstart: list | None) -> None:
+        """mosrx_slot_steer: arm the slot's next group submit (host pointers per
+        batch: n indices, STEER_QSLOTS queue starts); None, None disarms."""
+        if idx is None:
+            self._steer_arm = None
+            _chk(lib().mosrx_slot_steer(self.handle, slot, None, None), "mosrx_slot_steer")
+            return
+        # the pointer arrays must outlive the submit
+        self._steer_arm = ((C.c_void_p * len(idx))(*idx), (C.c_void_p * len(qstart))(*qstart))
+        _chk(lib().mosrx_slot_steer(self.handle, slot, *self._steer_arm), "mosrx_slot_steer")
+
     def group_wait(self, slot: int) -> None:
         _chk(lib().mosrx_classify_host_wait(self.handle, slot), "mosrx_classify_host_wait")
 
@@ -863,10 +897,15 @@ class Context:
                 d.d_tinfo = DevBuffer(self, max(d.n * 12, 12))
             if op in (OP_BPF, OP_CLASSIFY_BPF) and d.d_match is None:
                 d.d_match = DevBuffer(self, max(d.n * 4, 4))
+            if op == OP_STEER and d.d_sidx is None:
+                d.d_sidx = DevBuffer(self, max(d.n * 4, 4))
         bs = (Batch * len(dbs))(*[d.batch() for d in dbs])
-        outs = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_BPF else d.d_out.ptr) for d in dbs])
+        # OP_STEER reads the records a classify call left: the compact ones for arg == 8
+        outs = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_BPF else
+                                          d.d_out8.ptr if op == OP_STEER and arg == 8 else d.d_out.ptr) for d in dbs])
         aux = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_CLASSIFY_BPF else
                                          d.d_tinfo.ptr if op == OP_CLASSIFY_TI else
+                                         d.d_sidx.ptr if op == OP_STEER else
                                          (d.d_fhash.ptr if d.d_fhash else None)) for d in dbs])
         tot, avg = C.c_float(), C.c_float()
         _chk(lib().mosrx_time_op(self.handle, op, arg, bs, len(dbs), outs, aux, iters, nstreams,
@@ -972,6 +1011,16 @@ class Queue:
                                              C.byref(h)), "mosrx_queue_create_ex")
         self.handle = h.value
 
+    def set_steer(self, idx: list | None, qstart: list | None) -> None:
+        """mosrx_queue_set_steer: attach per-batch steer outputs (device pointers:
+        n indices, STEER_QSLOTS queue starts) to every run; None, None detaches."""
+        if idx is None:
+            _chk(lib().mosrx_queue_set_steer(self.ctx.handle, self.handle, None, None), "mosrx_queue_set_steer")
+            return
+        i = (C.c_void_p * len(idx))(*idx)
+        q = (C.c_void_p * len(qstart))(*qstart)
+        _chk(lib().mosrx_queue_set_steer(self.ctx.handle, self.handle, i, q), "mosrx_queue_set_steer")
+
     def run(self, sync: bool = True):
         _chk(lib().mosrx_queue_run(self.ctx.handle, self.handle, None), "mosrx_queue_run")
         if sync:
@@ -1036,6 +1085,7 @@ PKT_RX_RSS, DRV_NAME, PKT_RX_RESULTS, PKT_RX_MATCH = 0x03, 0x08, 0x10, 0x11
 PKT_RX_TCPINFO, PKT_SET_PARAMS = 0x12, 0x13
 PKT_RX_STATE, PKT_RX_RECLASSIFY, PKT_SET_BPF, PKT_RX_FHASH = 0x14, 0x15, 0x16, 0x17
 PKT_RX_RESULTS8 = 0x18
+PKT_RX_STEER = 0x19
 
 
 class IoModuleFunc(C.Structure):
@@ -1062,7 +1112,7 @@ class GpuBackend:
                  ngpu: int = 1, bpf=None, group: int = 1, tcpinfo: bool = False, tx_batch: int = 64,
                  timing: bool = False, flowhash: bool = False, tx_csum: bool = False, compact: bool = False,
                  group_bytes: int = 0, group_max_us: int = 0, direct_kb: int | None = None,
-                 direct_frames: int | None = None, module_lib=None):
+                 direct_frames: int | None = None, module_lib=None, steer: bool = False):
         self.L = L = module_lib or lib()
         cfg = ModuleCfg()
         L.mosrx_gpu_module_cfg_default(C.byref(cfg))
@@ -1081,6 +1131,7 @@ class GpuBackend:
             cfg.direct_kb = direct_kb       # copy-free groups up to this many KiB (0: none)
         if direct_frames is not None:
             cfg.direct_frames = direct_frames   # ... and up to this many frames
+        cfg.steer = int(steer)              # every group steered on the GPU (steer_view, run_loop_queues)
         if params is not None:
             cfg.params = params
         self.params = Params.from_buffer_copy(cfg.params)
@@ -1147,6 +1198,26 @@ class GpuBackend:
         if self._ioctl(self.ctx, ifidx, PKT_RX_TCPINFO, C.byref(p)):
             raise MosrxError(5, "dev_ioctl(MOSRX_PKT_RX_TCPINFO)")
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), (n * 12,)).view(TCPINFO_DTYPE).copy()
+
+    def steer_view(self, ifidx: int):
+        """dev_ioctl(MOSRX_PKT_RX_STEER): (idx[n], qstart[STEER_QSLOTS], num_queues)
+        of the exposed batch, or None when the backend does not steer."""
+        v = SteerView()
+        if self._ioctl(self.ctx, ifidx, PKT_RX_STEER, C.byref(v)):
+            return None
+        idx = np.ctypeslib.as_array(C.cast(v.idx, C.POINTER(C.c_uint32)), (max(v.n, 1),))[:v.n].copy()
+        qs = np.ctypeslib.as_array(C.cast(v.qstart, C.POINTER(C.c_uint32)), (STEER_QSLOTS,)).copy()
+        return idx, qs, int(v.num_queues)
+
+    def run_loop_queues(self, nq: int, fn=None, args: list | None = None, max_rounds: int = 0) -> RxStats:
+        """mosrx_rx_loop_queues over this backend: fn (a _PKTFN callback) gets
+        args[q] (integers passed as the void * argument) for queue q's frames."""
+        st = RxStats()
+        a = (C.c_void_p * nq)(*(args if args is not None else [None] * nq))
+        _chk(lib().mosrx_rx_loop_queues(C.addressof(self.m), self.ctx, self.nif, nq,
+                                        C.cast(fn, C.c_void_p) if fn is not None else None, a, max_rounds,
+                                        C.byref(st)), "mosrx_rx_loop_queues")
+        return st
 
     def set_params(self, ifidx: int, params: Params) -> int:
         """dev_ioctl(MOSRX_PKT_SET_PARAMS): the stack state changed (0 or -1)."""
