@@ -280,6 +280,39 @@ int  mosrx_queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx,
  * Both NULL disarms.  -EBUSY while the slot runs. */
 int  mosrx_slot_steer(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart);
 
+/* ---- queue-major gather: each queue's share as contiguous runs -------------- */
+/* The steer forms with extra outputs in the order of idx, written by the
+ * scatter launch (its gather form; histogram and scan are the same launches):
+ *   qrec[n * rec_bytes]   qrec[j] = rec[idx[j]], whole records
+ *   qoff[n], qlen[n]      off[idx[j]], len[idx[j]] of the batch's descriptors;
+ *                         both given or both NULL (NULL: records only)
+ * Queue q's share of the batch is then three contiguous runs from qstart[q]:
+ * over the batch's frame buffer, a batch in the library's own descriptor form,
+ * the ring a NIC would have filled for that core.  rec and qrec must be
+ * aligned to rec_bytes, qoff (and off) to 4, qlen (and len) to 2: -EINVAL
+ * otherwise.  Per frame the pass reads 6 more bytes and writes rec_bytes + 6
+ * more than the plain scatter. */
+/* mosrx_steer_dev with the gather outputs; d_off / d_len are the batch's
+ * descriptors (may be NULL with d_qoff / d_qlen NULL).  Same scratch
+ * (mosrx_steer_scratch_bytes), allocates nothing, graph-capturable; n == 0
+ * returns 0 and launches nothing. */
+int  mosrx_steer_gather_dev(mosrx_ctx *c, const void *d_rec, const uint32_t *d_off, const uint16_t *d_len,
+                            uint32_t n, int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart, void *d_qrec,
+                            uint32_t *d_qoff, uint16_t *d_qlen, void *d_scratch, size_t scratch_bytes,
+                            void *stream);
+/* mosrx_queue_set_steer with per-batch gather outputs (d_qrec[i]: n_i records
+ * of the queue's record size; d_qoff / d_qlen: both arrays or both NULL); the
+ * descriptors gathered are the queue's own batches'.  All five NULL detaches,
+ * as mosrx_queue_set_steer(c, q, NULL, NULL) does. */
+int  mosrx_queue_set_steer_gather(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
+                                  void *const *d_qrec, uint32_t *const *d_qoff, uint16_t *const *d_qlen);
+/* mosrx_slot_steer with gather outputs, under its rules: one-shot, written in
+ * place for a direct group whose outputs (these included) are all pinned, else
+ * copied back with the records; the slot's gather buffers are part of
+ * mosrx_classify_host_reserve.  All five NULL disarms. */
+int  mosrx_slot_steer_gather(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart,
+                             void *const *h_qrec, uint32_t *const *h_qoff, uint16_t *const *h_qlen);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned
@@ -437,7 +470,9 @@ enum { MOSRX_OP_CLASSIFY = 0, MOSRX_OP_CLASSIFY_FH = 1, MOSRX_OP_BPF = 2, MOSRX_
        MOSRX_OP_TX_CHECKS = 6 /* out[i]: mosrx_tx_check records, `arg` the flags */,
        MOSRX_OP_STEER = 7 /* the steer sequence over records already made: out[i] the records of batch i,
                            * aux[i] its idx array, `arg` = rec_bytes (8 or 16); qstart and scratch are the
-                           * timing call's own.  Three launches: -ENOTSUP from mosrx_time_op_dispatch */ };
+                           * timing call's own.  Three launches: -ENOTSUP from mosrx_time_op_dispatch */,
+       MOSRX_OP_STEER_GATHER = 8 /* MOSRX_OP_STEER with the scatter launch in its gather form: the batch's off / len
+                                  * (device resident) are gathered too, into outputs of the timing call's own */ };
 int  mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t nb, void *const *out,
                    void *const *aux, uint32_t iters, uint32_t nstreams, float *total_ms, float *avg_kernel_ms);
 /* The kernel's own duration, averaged over `iters` back-to-back launches on

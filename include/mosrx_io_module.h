@@ -94,6 +94,20 @@ typedef struct mosrx_steer_view {
 	uint32_t n;
 	uint32_t num_queues;         /* of the netdev's stack state: queues num_queues.. are empty */
 } mosrx_steer_view;
+#define MOSRX_PKT_RX_QUEUE   0x1A   /* argp: mosrx_queue_view * -- queue `q`'s share of the exposed batch as
+                                     * contiguous runs (cfg.steer = 2: the steer pass also gathered records,
+                                     * offsets and lengths in queue order); -1 unless the batch was gathered */
+typedef struct mosrx_queue_view {
+	uint32_t q;                  /* in: the queue, below MOSRX_STEER_QSLOTS - 1; or MOSRX_QUEUE_PROBE */
+	uint32_t n;                  /* out: its frames in the exposed batch; the arrays below start at qstart[q] */
+	const uint8_t *rec;          /* n records of rec_bytes, in arrival order */
+	uint32_t rec_bytes;          /* 16 (mosrx_result) or 8 (mosrx_result8) */
+	const uint32_t *off;         /* frame j of the share is frames + off[j], */
+	const uint16_t *len;         /*   len[j] bytes, */
+	const uint32_t *idx;         /*   and was frame idx[j] of the batch */
+	const uint8_t *frames;       /* the batch's frame base */
+} mosrx_queue_view;
+#define MOSRX_QUEUE_PROBE 0xFFFFFFFFu   /* q: only ask whether the backend gathers (0 / -1; no batch needed, n = 0) */
 typedef struct mosrx_rx_state {
 	uint32_t num_msp, num_esp;   /* the stack state of the batch's verdicts */
 	uint32_t gen;                /* the netdev's parameter / filter generation they were made with */
@@ -246,7 +260,10 @@ typedef struct mosrx_gpu_module_cfg {
 	                                                 * frame indices partitioned by the records' queue
 	                                                 * (GetRSSCPUCore), arrival order kept within a queue
 	                                                 * (dev_ioctl(MOSRX_PKT_RX_STEER), mosrx_rx_loop_queues);
-	                                                 * a lone batch then takes the group path.  Default 0 */
+	                                                 * a lone batch then takes the group path.  2: ... and
+	                                                 * gathered queue-major (records, offsets, lengths in the
+	                                                 * order of idx: dev_ioctl(MOSRX_PKT_RX_QUEUE), the hub).
+	                                                 * Default 0 */
 } mosrx_gpu_module_cfg;
 #define MOSRX_GROUP_AUTO        0
 #define MOSRX_DIRECT_DEFAULT_FRAMES 0xFFFFFFFFu   /* no frame limit: a 16K limit made the 64 B 90 % points
@@ -371,11 +388,62 @@ int mosrx_rx_loop_ex(const io_module_func *iom, struct mtcp_thread_context *ctx,
  * index in the batch.  Frames of queues >= nq (none when nq is the stack's
  * num_queues) are counted in the stats and handed to nobody.  Rounds as
  * mosrx_rx_loop: it ends at the first idle round, or after `max_rounds`
- * rounds (0: no limit).  -ENOTSUP when the backend does not steer.  The hub
- * that hands each queue's frames to another thread's recv_pkts is not here:
- * DESIGN.md §7. */
+ * rounds (0: no limit).  -ENOTSUP when the backend does not steer.  Over a
+ * gathering backend (cfg.steer = 2) each queue is read through its contiguous
+ * MOSRX_PKT_RX_QUEUE view instead of through idx: the same calls to fn in the
+ * same order, the same stats.  The hub below hands each queue's frames to
+ * another thread's recv_pkts. */
 int mosrx_rx_loop_queues(const io_module_func *iom, struct mtcp_thread_context *ctx, int nif, uint32_t nq,
                          mosrx_pkt_fn fn, void *const *arg, uint64_t max_rounds, mosrx_rx_stats *st);
+
+/* ---- the hub: one steering backend, one io_module endpoint per core ---------
+ * mOS runs one mTCP thread per core, each calling its own recv_pkts
+ * (core.c:1369-1466); a pcap file, an AF_PACKET ring or a memory source
+ * enters through one thread.  The hub wraps one backend opened with
+ * cfg.steer = 2 and gives core q a context for mosrx_hub_module_func, whose
+ * recv_pkts returns the size of queue q's share of the current batch,
+ * get_rptr(i) the share's i-th frame, and dev_ioctl its records
+ * (MOSRX_PKT_RX_RESULTS / RX_RESULTS8: the contiguous gathered run),
+ * MOSRX_PKT_RX_STATE, and MOSRX_PKT_RX_QUEUE (the share's own view: idx[i] is
+ * frame i's index in the backend's batch).  mosrx_rx_loop runs over an
+ * endpoint unchanged.  Two rules:
+ *   - only the owner calls the backend: core 0's endpoint, on the thread that
+ *     opened the hub (which must be the thread that opened the backend); no
+ *     backend or HIP call is made from another core's thread.  The owner's
+ *     recv_pkts from any other thread returns -1.
+ *   - a batch goes back only when every core is done with its share: the hub
+ *     keeps an epoch and a countdown of the cores that have not yet moved past
+ *     the current batch.  A core moves past when its next recv_pkts arrives
+ *     after it took its share (an empty share counts at once); the owner calls
+ *     the backend's recv_pkts, which takes the lent batch back, only at
+ *     countdown zero.
+ * Nothing blocks: a core's recv_pkts that finds no new epoch returns 0, and so
+ * does the owner's while the countdown is above zero -- the idle round every
+ * recv_pkts may return (C11 atomics, acquire / release on the epoch and the
+ * countdown; no locks, no waits).  Frames of queues >= ncores are counted
+ * (mosrx_hub_stats.unowned) and handed to nobody.  The backend stays pipelined
+ * across its two slots; one batch is exposed at a time. */
+typedef struct mosrx_hub mosrx_hub;
+typedef struct mosrx_hub_stats {
+	uint64_t batches;            /* backend batches published to the cores */
+	uint64_t frames;             /* their frames */
+	uint64_t delivered;          /* frames in the cores' shares */
+	uint64_t unowned;            /* frames of queues >= ncores */
+	uint64_t owner_waits;        /* owner recv_pkts that returned 0 because a share was outstanding */
+} mosrx_hub_stats;
+#define MOSRX_HUB_MAX_CORES 64
+/* -EINVAL; -ENOTSUP over a backend that does not gather (MOSRX_QUEUE_PROBE);
+ * -ENOMEM.  The backend is the caller's: the hub neither opens nor closes it. */
+int mosrx_hub_open(const io_module_func *backend, struct mtcp_thread_context *backend_ctx, int nif,
+                   uint32_t ncores, mosrx_hub **out);
+/* Core `core`'s context for mosrx_hub_module_func (NULL: no such core); it
+ * lives until mosrx_hub_close. */
+struct mtcp_thread_context *mosrx_hub_endpoint(mosrx_hub *hub, uint32_t core);
+/* The owner's counters; call it on the owner's thread (or after the cores' threads are joined). */
+int mosrx_hub_stats_get(const mosrx_hub *hub, mosrx_hub_stats *st);
+/* -EBUSY while a share is outstanding (some core has not moved past the current batch); else frees the hub. */
+int mosrx_hub_close(mosrx_hub *hub);
+extern io_module_func mosrx_hub_module_func;
 
 /* A consumer for mosrx_rx_loop*: the frames mOS forwards with `forward` set,
  * decided from the verdict reason and the stack state as ProcessPacket's paths

@@ -75,6 +75,10 @@ struct stage {
 	uint32_t *fh;             /* pinned, flow-table hashes (cfg.flowhash) */
 	uint32_t *sidx, *sqs;     /* pinned, queue steering (cfg.steer): n indices, MOSRX_STEER_QSLOTS starts */
 	int steered;              /* its last launch filled them (MOSRX_PKT_RX_STEER) */
+	uint8_t *qrec;            /* pinned, the queue-major gather (cfg.steer = 2): n records in the order of sidx, */
+	uint32_t *qoff;           /*   their offsets */
+	uint16_t *qlen;           /*   and lengths */
+	int gathered;             /* its last launch filled them (MOSRX_PKT_RX_QUEUE) */
 	uint32_t n, max_len;
 	uint32_t rec0;            /* its first record's index in the group's record arrays */
 	uint32_t stride;          /* frame i at off[0] + i * stride (a fixed-size packing), else 0: the layout hint */
@@ -101,6 +105,9 @@ struct group {
 	uint32_t *match;
 	uint32_t *fh;
 	uint32_t *sidx, *sqs;     /* cfg.steer: rec_cap indices, cap_st x MOSRX_STEER_QSLOTS queue starts */
+	uint8_t *sqrec;           /* cfg.steer = 2: rec_cap gathered records (16-byte slots), */
+	uint32_t *sqoff;          /*   offsets */
+	uint16_t *sqlen;          /*   and lengths */
 	uint64_t rec_cap;         /* frames the record arrays hold */
 	struct stage *st;         /* cap_st stages */
 	uint32_t cap_st;
@@ -417,6 +424,9 @@ static void group_free(mosrx_ctx *mc, struct group *g)
 	if (g->fh) mosrx_host_free(mc, g->fh);
 	if (g->sidx) mosrx_host_free(mc, g->sidx);
 	if (g->sqs) mosrx_host_free(mc, g->sqs);
+	if (g->sqrec) mosrx_host_free(mc, g->sqrec);
+	if (g->sqoff) mosrx_host_free(mc, g->sqoff);
+	if (g->sqlen) mosrx_host_free(mc, g->sqlen);
 	free(g->st);
 	memset(g, 0, sizeof(*g));
 }
@@ -488,7 +498,10 @@ static int group_alloc_sized(mosrx_ctx *mc, struct group *g, uint64_t bytes)
 	    (MATCH_UP_FRONT && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->match)) ||
 	    (g_cfg.flowhash && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->fh)) ||
 	    (g_cfg.steer && (mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sidx) ||
-	                     mosrx_host_alloc(mc, (size_t)g->cap_st * MOSRX_STEER_QSLOTS * 4, (void **)&g->sqs))))
+	                     mosrx_host_alloc(mc, (size_t)g->cap_st * MOSRX_STEER_QSLOTS * 4, (void **)&g->sqs))) ||
+	    (g_cfg.steer == 2 && (mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_result), (void **)&g->sqrec) ||
+	                          mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sqoff) ||
+	                          mosrx_host_alloc(mc, g->rec_cap * 2, (void **)&g->sqlen))))
 		return -ENOMEM;
 	return 0;
 }
@@ -729,6 +742,9 @@ static void group_fill(struct if_state *is, struct group *g)
 		s->sidx = g->sidx ? g->sidx + recs : NULL;
 		s->sqs = g->sqs ? g->sqs + (size_t)i * MOSRX_STEER_QSLOTS : NULL;
 		s->steered = 0;
+		s->qoff = g->sqoff ? g->sqoff + recs : NULL;
+		s->qlen = g->sqlen ? g->sqlen + recs : NULL;
+		s->gathered = 0;
 		if (!s->n)
 			break;
 		g->nst++;
@@ -806,6 +822,10 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	mosrx_tcpinfo *ti[MOSRX_MAX_GROUP];
 	uint32_t *fh[MOSRX_MAX_GROUP], *mt[MOSRX_MAX_GROUP];
 	uint32_t *sx[MOSRX_MAX_GROUP], *sq[MOSRX_MAX_GROUP];
+	void *gr[MOSRX_MAX_GROUP];
+	uint32_t *go[MOSRX_MAX_GROUP];
+	uint16_t *gl[MOSRX_MAX_GROUP];
+	const int gather = g_cfg.steer == 2 && g->sqrec;
 	uint32_t i, nb = g->nst - first;
 	int rc;
 	if (follow_mos_state(pv, is))
@@ -824,6 +844,12 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 		sx[i - first] = s->sidx;
 		sq[i - first] = s->sqs;
 		s->steered = g_cfg.steer && s->sidx && s->sqs;
+		/* the gathered records' slots: the size of the records themselves */
+		s->qrec = gather ? g->sqrec + (size_t)s->rec0 * (compact ? sizeof(mosrx_result8) : sizeof(mosrx_result)) : NULL;
+		gr[i - first] = s->qrec;
+		go[i - first] = s->qoff;
+		gl[i - first] = s->qlen;
+		s->gathered = s->steered && gather;
 		s->msp = is->params.num_msp;
 		s->esp = is->params.num_esp;
 		s->gen = is->gen;
@@ -834,7 +860,8 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	}
 	/* cfg.steer: every group is armed (the submit below takes the arm; sx / sq
 	 * are read before it returns) */
-	if (g_cfg.steer && mosrx_slot_steer(is->mc, k, sx, sq))
+	if (g_cfg.steer && (gather ? mosrx_slot_steer_gather(is->mc, k, sx, sq, gr, go, gl)
+	                           : mosrx_slot_steer(is->mc, k, sx, sq)))
 		return -1;
 	if (compact && is->nprog)   /* 8-byte records + the set's masks: the fused kernel's 8-byte form */
 		rc = mosrx_classify_host_group_submit_bpf_c8(is->mc, k, b, nb, out8, g_cfg.flowhash ? fh : NULL, mt);
@@ -1197,6 +1224,29 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 		v->qstart = s->sqs;
 		v->n = s->n;
 		v->num_queues = (uint32_t)pv->ifs[nif].params.num_queues;
+		return 0;
+	}
+	case MOSRX_PKT_RX_QUEUE: {
+		mosrx_queue_view *v = argp;
+		uint32_t q0, q1;
+		if (v->q == MOSRX_QUEUE_PROBE) {   /* does this backend gather at all (no batch needed) */
+			memset(v, 0, sizeof(*v));
+			v->q = MOSRX_QUEUE_PROBE;
+			return g_cfg.steer == 2 ? 0 : -1;
+		}
+		if (!s || !s->steered || !s->gathered || !v || v->q >= MOSRX_STEER_QSLOTS - 1)
+			return -1;
+		q0 = s->sqs[v->q];
+		q1 = s->sqs[v->q + 1];
+		if (q0 > q1 || q1 > s->n)
+			return -1;
+		v->n = q1 - q0;
+		v->rec_bytes = s->compact ? (uint32_t)sizeof(mosrx_result8) : (uint32_t)sizeof(mosrx_result);
+		v->rec = s->qrec + (size_t)q0 * v->rec_bytes;
+		v->off = s->qoff + q0;
+		v->len = s->qlen + q0;
+		v->idx = s->sidx + q0;
+		v->frames = s->frames;
 		return 0;
 	}
 	case MOSRX_PKT_RX_TCPINFO:

@@ -204,6 +204,9 @@ int mosrx_open(int device, const mosrx_params *p, mosrx_ctx **out)
 		    hipHostMalloc((void **)&c->slot[i].h_sdesc, MOSRX_MAX_GROUP * sizeof(mosrx_sdesc),
 		                  hipHostMallocDefault) != hipSuccess ||
 		    hipMalloc((void **)&c->slot[i].d_sqstart, (size_t)MOSRX_MAX_GROUP * MOSRX_STEER_QSLOTS * 4) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_gdesc, MOSRX_MAX_GROUP * sizeof(mosrx_gdesc)) != hipSuccess ||
+		    hipHostMalloc((void **)&c->slot[i].h_gdesc, MOSRX_MAX_GROUP * sizeof(mosrx_gdesc),
+		                  hipHostMallocDefault) != hipSuccess ||
 		    hipMalloc((void **)&c->slot[i].d_cnt, MOSRX_CNT_WORDS * 4) != hipSuccess ||
 		    hipHostMalloc((void **)&c->slot[i].h_cnt, MOSRX_CNT_WORDS * 4, hipHostMallocDefault) != hipSuccess ||
 		    !(c->slot[i].h_prev = calloc(MOSRX_CNT_WORDS, 4))) {
@@ -236,7 +239,11 @@ static void slot_free(struct slot *s)
 	if (s->d_match) hipFree(s->d_match);
 	if (s->d_sidx) hipFree(s->d_sidx);
 	if (s->d_shist) hipFree(s->d_shist);
+	if (s->d_sqrec) hipFree(s->d_sqrec);
+	if (s->d_sqoff) hipFree(s->d_sqoff);
+	if (s->d_sqlen) hipFree(s->d_sqlen);
 	s->d_sidx = NULL; s->d_shist = NULL;
+	s->d_sqrec = NULL; s->d_sqoff = NULL; s->d_sqlen = NULL;
 	s->d_frames = NULL; s->d_off = NULL; s->d_len = NULL; s->d_res = NULL; s->d_fh = NULL; s->d_ti = NULL;
 	s->d_match = NULL;
 	s->cap_frames = 0; s->cap_n = 0;
@@ -270,6 +277,8 @@ void mosrx_close(mosrx_ctx *c)
 		if (c->slot[i].d_sdesc) hipFree(c->slot[i].d_sdesc);
 		if (c->slot[i].h_sdesc) hipHostFree(c->slot[i].h_sdesc);
 		if (c->slot[i].d_sqstart) hipFree(c->slot[i].d_sqstart);
+		if (c->slot[i].d_gdesc) hipFree(c->slot[i].d_gdesc);
+		if (c->slot[i].h_gdesc) hipHostFree(c->slot[i].h_gdesc);
 		if (c->slot[i].d_cnt) hipFree(c->slot[i].d_cnt);
 		if (c->slot[i].h_cnt) hipHostFree(c->slot[i].h_cnt);
 		free(c->slot[i].h_prev);
@@ -643,7 +652,10 @@ int mosrx__slot_reserve(mosrx_ctx *c, struct slot *s, uint64_t frames_bytes, uin
 		    hipMalloc((void **)&s->d_ti, (size_t)nn * sizeof(mosrx_tcpinfo)) != hipSuccess ||
 		    hipMalloc((void **)&s->d_match, (size_t)nn * 4) != hipSuccess ||
 		    hipMalloc((void **)&s->d_sidx, (size_t)nn * 4) != hipSuccess ||
-		    hipMalloc((void **)&s->d_shist, steer_group_scratch(nn)) != hipSuccess) {
+		    hipMalloc((void **)&s->d_shist, steer_group_scratch(nn)) != hipSuccess ||
+		    hipMalloc((void **)&s->d_sqrec, (size_t)nn * sizeof(mosrx_result)) != hipSuccess ||
+		    hipMalloc((void **)&s->d_sqoff, (size_t)nn * 4) != hipSuccess ||
+		    hipMalloc((void **)&s->d_sqlen, (size_t)nn * 2) != hipSuccess) {
 			slot_free(s);
 			return -ENOMEM;
 		}
@@ -1039,13 +1051,41 @@ static int steer_outputs(int device, const mosrx_batch *b, uint32_t nb, uint32_t
 	return 1;
 }
 
+/* The armed gather outputs of a group (mosrx_slot_steer_gather). */
+struct gather_out {
+	void *const *qrec;          /* NULL: a plain steer */
+	uint32_t *const *qoff;      /* NULL with qlen: records only */
+	uint16_t *const *qlen;
+};
+
+/* ... and for its gather outputs, into the slot's gather table gd[]. */
+static int gather_outputs(int device, const mosrx_batch *b, uint32_t nb, size_t rsz, const struct gather_out *g,
+                          mosrx_gdesc *gd)
+{
+	uint32_t i;
+	for (i = 0; i < nb; i++) {
+		gd[i].qrec = NULL;
+		gd[i].qoff = NULL;
+		gd[i].qlen = NULL;
+		if (!b[i].n)
+			continue;
+		if (!(gd[i].qrec = mosrx__host_dev_of(g->qrec[i], (uint64_t)b[i].n * rsz, device)) ||
+		    (g->qoff && (!(gd[i].qoff = mosrx__host_dev_of(g->qoff[i], (uint64_t)b[i].n * 4, device)) ||
+		                 !(gd[i].qlen = mosrx__host_dev_of(g->qlen[i], (uint64_t)b[i].n * 2, device)))))
+			return 0;
+	}
+	return 1;
+}
+
 /* The steer launches of an armed group, behind its classify launch on the
  * slot's stream: over the records where that launch wrote them (s->h_qdesc),
  * into the caller's pinned arrays (in_place: steer_outputs filled the table)
  * or the slot's buffers, which are then copied back -- one copy per run of
- * batches whose host arrays follow each other. */
+ * batches whose host arrays follow each other.  With gather outputs armed
+ * (g->qrec) the scatter pass is its gather form, over the descriptors where
+ * the classify launch read them. */
 static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
-                       uint32_t *const *h_idx, uint32_t *const *h_qstart)
+                       uint32_t *const *h_idx, uint32_t *const *h_qstart, const struct gather_out *g)
 {
 	mosrx_sparams sp;
 	uint32_t i, tiles = 0;
@@ -1062,8 +1102,23 @@ static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t
 		d->n = b[i].n;
 		d->tile_base = tiles;
 		tiles += (b[i].n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
+		if (g->qrec) {
+			mosrx_gdesc *gd = &s->h_gdesc[i];
+			if (!in_place) {
+				gd->qrec = b[i].n ? s->d_sqrec + pre * rsz : NULL;
+				gd->qoff = b[i].n && g->qoff ? s->d_sqoff + pre : NULL;
+				gd->qlen = b[i].n && g->qoff ? s->d_sqlen + pre : NULL;
+			}
+			gd->off = s->h_qdesc[i].off;
+			gd->len = s->h_qdesc[i].len;
+		}
 	}
 	HIPCHK(hipMemcpyAsync(s->d_sdesc, s->h_sdesc, nb * sizeof(mosrx_sdesc), hipMemcpyHostToDevice, s->stream));
+	if (g->qrec) {
+		HIPCHK(hipMemcpyAsync(s->d_gdesc, s->h_gdesc, nb * sizeof(mosrx_gdesc), hipMemcpyHostToDevice, s->stream));
+		sp.gdesc = s->d_gdesc;
+		sp.gather = 1;
+	}
 	sp.desc = s->d_sdesc;
 	sp.hist = s->d_shist;
 	sp.nb = nb;
@@ -1071,6 +1126,16 @@ static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t
 	sp.total_tiles = tiles;
 	if ((rc = mosrx_launch_steer(&sp, s->stream)))
 		return rc;
+	for (i = 0, pre = 0; g->qrec && !in_place && i < nb; pre += b[i].n, i++) {
+		if (!b[i].n)
+			continue;
+		HIPCHK(hipMemcpyAsync(g->qrec[i], s->d_sqrec + pre * rsz, (size_t)b[i].n * rsz, hipMemcpyDeviceToHost,
+		                      s->stream));
+		if (g->qoff) {
+			HIPCHK(hipMemcpyAsync(g->qoff[i], s->d_sqoff + pre, (size_t)b[i].n * 4, hipMemcpyDeviceToHost, s->stream));
+			HIPCHK(hipMemcpyAsync(g->qlen[i], s->d_sqlen + pre, (size_t)b[i].n * 2, hipMemcpyDeviceToHost, s->stream));
+		}
+	}
 	for (i = 0, pre = 0; !in_place && i < nb;) {
 		uint32_t j = i + 1;
 		uint64_t n = b[i].n;
@@ -1113,6 +1178,7 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	int rc, unknown = 0, kind, tpb_ok = 1;
 	int fused = 0, uni = 0, direct, out_direct;
 	uint32_t *const *h_sidx, *const *h_sqs;
+	struct gather_out go;
 	if (!c || slot < 0 || slot >= NSLOT || !b || !h_out || nb == 0 || nb > MOSRX_MAX_GROUP ||
 	    (h_match && h_tcpinfo) || (compact && h_tcpinfo))
 		return -EINVAL;
@@ -1122,13 +1188,20 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	/* mosrx_slot_steer armed this submit, whatever becomes of it */
 	h_sidx = s->steer_idx;
 	h_sqs = s->steer_qstart;
+	go = (struct gather_out){s->steer_qrec, s->steer_qoff, s->steer_qlen};
 	s->steer_idx = s->steer_qstart = NULL;
+	s->steer_qrec = NULL;
+	s->steer_qoff = NULL;
+	s->steer_qlen = NULL;
 	for (i = 0; i < nb; i++) {
 		if ((rc = mosrx__check_batch(&b[i], 0)))
 			return rc;
 		if (b[i].n && (!h_out[i] || (h_tcpinfo && !h_tcpinfo[i]) || (h_fhash && !h_fhash[i]) ||
 		               (h_match && !h_match[i]) ||
-		               (h_sidx && (!h_sidx[i] || !h_sqs[i] || (((uintptr_t)h_sidx[i] | (uintptr_t)h_sqs[i]) & 3)))))
+		               (h_sidx && (!h_sidx[i] || !h_sqs[i] || (((uintptr_t)h_sidx[i] | (uintptr_t)h_sqs[i]) & 3))) ||
+		               (go.qrec && (!go.qrec[i] || ((uintptr_t)go.qrec[i] & (rsz - 1)))) ||
+		               (go.qoff && (!go.qoff[i] || !go.qlen[i] || ((uintptr_t)go.qoff[i] & 3) ||
+		                            ((uintptr_t)go.qlen[i] & 1)))))
 			return -EINVAL;
 		if (!b[i].max_len)
 			unknown = 1;
@@ -1151,7 +1224,8 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	HIPCHK(hipSetDevice(c->device));
 	direct = direct_regions(c, s, r, nr, ntot, &dev_bytes);
 	out_direct = direct && direct_outputs(c->device, b, nb, h_out, rsz, h_tcpinfo, h_fhash, h_match, od) &&
-	             (!h_sidx || steer_outputs(c->device, b, nb, h_sidx, h_sqs, s->h_sdesc));
+	             (!h_sidx || steer_outputs(c->device, b, nb, h_sidx, h_sqs, s->h_sdesc)) &&
+	             (!go.qrec || gather_outputs(c->device, b, nb, rsz, &go, s->h_gdesc));
 	if (!direct) {
 		group_copy(s, r, nr, &dev_bytes, 0);
 		if ((rc = mosrx__slot_reserve(c, s, dev_bytes, ntot)))
@@ -1240,7 +1314,7 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	if (c->timing && h_match && !fused)
 		HIPCHK(hipEventRecord(s->kev1, s->stream));
 	s->timed = c->timing;
-	if (h_sidx && (rc = group_steer(s, b, nb, rsz, out_direct, h_sidx, h_sqs)))
+	if (h_sidx && (rc = group_steer(s, b, nb, rsz, out_direct, h_sidx, h_sqs, &go)))
 		return rc;
 	/* results: one copy when the host buffers follow each other, else per batch */
 	for (i = 0, pre = 0; !out_direct && i < nb;) {
@@ -1634,15 +1708,20 @@ int mosrx_time_host(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, mosrx_resul
 
 /* MOSRX_OP_STEER's qstart + scratch: one block for the context stream and one
  * per timing stream, each qstart (rounded to STEER_TMP_QS bytes) followed by
- * the scratch of the largest batch. */
+ * the scratch of the largest batch, then MOSRX_OP_STEER_GATHER's outputs for
+ * it (records of 16 bytes, offsets, lengths; each rounded to 256 bytes). */
 #define STEER_TMP_QS ((MOSRX_STEER_QSLOTS * 4 + 255) & ~255)
+#define STEER_TMP_RND(x) (((size_t)(x) + 255) & ~(size_t)255)
 static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
 {
 	uint32_t i, maxn = 0;
 	size_t stride, bytes;
 	for (i = 0; i < nb; i++)
 		maxn = b[i].n > maxn ? b[i].n : maxn;
-	stride = STEER_TMP_QS + ((mosrx_steer_scratch_bytes(maxn) + 255) & ~(size_t)255);
+	c->steer_tmp_scratch = STEER_TMP_RND(mosrx_steer_scratch_bytes(maxn));
+	c->steer_tmp_n = maxn;
+	stride = STEER_TMP_QS + c->steer_tmp_scratch + STEER_TMP_RND((size_t)maxn * 16) + STEER_TMP_RND((size_t)maxn * 4) +
+	         STEER_TMP_RND((size_t)maxn * 2);
 	bytes = stride * (MOSRX_MAX_STREAMS + 1);
 	if (bytes > c->steer_tmp_bytes) {
 		HIPCHK(hipDeviceSynchronize());
@@ -1678,7 +1757,19 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 			k++;
 		blk = c->steer_tmp + (size_t)(k < c->nxs ? k + 1 : 0) * c->steer_tmp_stride;
 		return mosrx_steer_dev(c, out, b->n, arg, (uint32_t *)aux, (uint32_t *)blk, blk + STEER_TMP_QS,
-		                       c->steer_tmp_stride - STEER_TMP_QS, s);
+		                       c->steer_tmp_scratch, s);
+	}
+	case MOSRX_OP_STEER_GATHER: {
+		uint32_t k = 0;
+		uint8_t *blk, *qrec, *qoff, *qlen;
+		while (k < c->nxs && c->xs[k] != s)
+			k++;
+		blk = c->steer_tmp + (size_t)(k < c->nxs ? k + 1 : 0) * c->steer_tmp_stride;
+		qrec = blk + STEER_TMP_QS + c->steer_tmp_scratch;
+		qoff = qrec + STEER_TMP_RND((size_t)c->steer_tmp_n * 16);
+		qlen = qoff + STEER_TMP_RND((size_t)c->steer_tmp_n * 4);
+		return mosrx_steer_gather_dev(c, out, b->off, b->len, b->n, arg, (uint32_t *)aux, (uint32_t *)blk, qrec,
+		                              (uint32_t *)qoff, (uint16_t *)qlen, blk + STEER_TMP_QS, c->steer_tmp_scratch, s);
 	}
 	default: return -EINVAL;
 	}
@@ -1766,13 +1857,13 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 {
 	int rc;
 	if (!c || !b || nb == 0 || iters == 0 || nstreams == 0 || nstreams > MOSRX_MAX_STREAMS ||
-	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER || (op != MOSRX_OP_TX_CSUM && !out) ||
+	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER_GATHER || (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI ||
-	      op == MOSRX_OP_STEER) && !aux) ||
-	    (op == MOSRX_OP_STEER && arg != 8 && arg != 16))
+	      op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && !aux) ||
+	    ((op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && arg != 8 && arg != 16))
 		return -EINVAL;
 	HIPCHK(hipSetDevice(c->device));
-	if (op == MOSRX_OP_STEER && (rc = steer_tmp_reserve(c, b, nb)))
+	if ((op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && (rc = steer_tmp_reserve(c, b, nb)))
 		return rc;
 	if (total_ms && (rc = time_streams(c, op, arg, b, nb, out, aux, iters, nstreams, total_ms)))
 		return rc;
@@ -1836,12 +1927,12 @@ int mosrx_time_op_dispatch(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, 
                            void *const *aux, uint32_t iters, float *avg_ms)
 {
 	struct op_run r = {op, arg, b, nb, out, aux};
-	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER ||
+	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER_GATHER ||
 	    (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI ||
-	      op == MOSRX_OP_STEER) && !aux))
+	      op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && !aux))
 		return -EINVAL;
-	if (op == MOSRX_OP_STEER)   /* three launches: no single dispatch to stamp */
+	if (op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER)   /* three launches: no single dispatch to stamp */
 		return -ENOTSUP;
 	/* (the BPF ops are one launch with the fused kernel / the set's own kernel;
 	 * classify + the set's kernel, two, is refused by the launch count) */
@@ -1971,6 +2062,10 @@ struct mosrx_queue {
 	uint32_t *d_shist;
 	uint32_t steer_tiles;
 	int steer;
+	/* its gather form (mosrx_queue_set_steer_gather): the table parallel to
+	 * d_sdesc; gather: the scatter pass of a run is the gather form */
+	mosrx_gdesc *d_gdesc;
+	int gather;
 };
 
 int mosrx_queue_create_ex(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, void *const *d_out,
@@ -2102,24 +2197,49 @@ int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 	sp.nb = q->nb;
 	sp.rec_bytes = q->compact ? 8u : 16u;
 	sp.total_tiles = q->steer_tiles;
+	if (q->gather) {
+		sp.gdesc = q->d_gdesc;
+		sp.gather = 1;
+	}
 	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
 }
 
-int mosrx_queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart)
+static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
+                           void *const *d_qrec, uint32_t *const *d_qoff, uint16_t *const *d_qlen)
 {
 	mosrx_sdesc *h;
+	mosrx_gdesc *g = NULL;
 	uint32_t i, tiles = 0;
-	if (!c || !q || !d_idx != !d_qstart)
+	if (!c || !q || !d_idx != !d_qstart || (d_qrec && !d_idx) || !d_qoff != !d_qlen || (d_qoff && !d_qrec))
 		return -EINVAL;
 	if (!d_idx) {
-		q->steer = 0;
+		q->steer = q->gather = 0;
 		return 0;
 	}
-	for (i = 0; i < q->nb; i++)
-		if (q->h_desc[i].n && (!d_idx[i] || !d_qstart[i] || (((uintptr_t)d_idx[i] | (uintptr_t)d_qstart[i]) & 3)))
+	for (i = 0; i < q->nb; i++) {
+		const uintptr_t rb = q->compact ? 8 : 16;
+		if (!q->h_desc[i].n)
+			continue;
+		if (!d_idx[i] || !d_qstart[i] || (((uintptr_t)d_idx[i] | (uintptr_t)d_qstart[i]) & 3))
 			return -EINVAL;
-	if (!(h = calloc(q->nb, sizeof(*h))))
+		if (d_qrec && (!d_qrec[i] || ((uintptr_t)d_qrec[i] & (rb - 1))))
+			return -EINVAL;
+		if (d_qoff && (!d_qoff[i] || !d_qlen[i] || ((uintptr_t)d_qoff[i] & 3) || ((uintptr_t)d_qlen[i] & 1)))
+			return -EINVAL;
+	}
+	if (!(h = calloc(q->nb, sizeof(*h))) || (d_qrec && !(g = calloc(q->nb, sizeof(*g))))) {
+		free(h);
 		return -ENOMEM;
+	}
+	for (i = 0; d_qrec && i < q->nb; i++) {
+		if (!q->h_desc[i].n)
+			continue;
+		g[i].off = q->h_desc[i].off;
+		g[i].len = q->h_desc[i].len;
+		g[i].qrec = d_qrec[i];
+		g[i].qoff = d_qoff ? d_qoff[i] : NULL;
+		g[i].qlen = d_qoff ? d_qlen[i] : NULL;
+	}
 	for (i = 0; i < q->nb; i++) {
 		h[i].rec = (const uint8_t *)q->h_desc[i].out;
 		h[i].n = q->h_desc[i].n;
@@ -2128,21 +2248,42 @@ int mosrx_queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, 
 		h[i].tile_base = tiles;
 		tiles += (h[i].n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
 	}
-	q->steer = 0;
+	q->steer = q->gather = 0;
 	if (hipSetDevice(c->device) != hipSuccess ||
 	    (!q->d_sdesc && hipMalloc((void **)&q->d_sdesc, (size_t)q->nb * sizeof(*h)) != hipSuccess) ||
+	    (g && !q->d_gdesc && hipMalloc((void **)&q->d_gdesc, (size_t)q->nb * sizeof(*g)) != hipSuccess) ||
 	    (!q->d_shist && hipMalloc((void **)&q->d_shist, ((size_t)tiles + 1) * MOSRX_STEER_BINS * 4) != hipSuccess)) {
 		free(h);
+		free(g);
 		return -ENOMEM;
 	}
-	if (hipMemcpy(q->d_sdesc, h, (size_t)q->nb * sizeof(*h), hipMemcpyHostToDevice) != hipSuccess) {
+	if (hipMemcpy(q->d_sdesc, h, (size_t)q->nb * sizeof(*h), hipMemcpyHostToDevice) != hipSuccess ||
+	    (g && hipMemcpy(q->d_gdesc, g, (size_t)q->nb * sizeof(*g), hipMemcpyHostToDevice) != hipSuccess)) {
 		free(h);
+		free(g);
 		return -EIO;
 	}
 	free(h);
+	free(g);
 	q->steer_tiles = tiles;
 	q->steer = 1;
+	q->gather = d_qrec != NULL;
 	return 0;
+}
+
+int mosrx_queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart)
+{
+	return queue_set_steer(c, q, d_idx, d_qstart, NULL, NULL, NULL);
+}
+
+int mosrx_queue_set_steer_gather(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
+                                 void *const *d_qrec, uint32_t *const *d_qoff, uint16_t *const *d_qlen)
+{
+	if (!d_idx && !d_qstart && !d_qrec && !d_qoff && !d_qlen)   /* all NULL detaches */
+		return queue_set_steer(c, q, NULL, NULL, NULL, NULL, NULL);
+	if (!d_qrec)
+		return -EINVAL;
+	return queue_set_steer(c, q, d_idx, d_qstart, d_qrec, d_qoff, d_qlen);
 }
 
 int mosrx_slot_steer(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart)
@@ -2153,6 +2294,25 @@ int mosrx_slot_steer(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *c
 		return -EBUSY;
 	c->slot[slot].steer_idx = h_idx;
 	c->slot[slot].steer_qstart = h_qstart;
+	c->slot[slot].steer_qrec = NULL;
+	c->slot[slot].steer_qoff = NULL;
+	c->slot[slot].steer_qlen = NULL;
+	return 0;
+}
+
+int mosrx_slot_steer_gather(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart,
+                            void *const *h_qrec, uint32_t *const *h_qoff, uint16_t *const *h_qlen)
+{
+	const int none = !h_idx && !h_qstart && !h_qrec && !h_qoff && !h_qlen;
+	if (!c || slot < 0 || slot >= NSLOT || (!none && (!h_idx || !h_qstart || !h_qrec)) || !h_qoff != !h_qlen)
+		return -EINVAL;
+	if (c->slot[slot].busy)
+		return -EBUSY;
+	c->slot[slot].steer_idx = h_idx;
+	c->slot[slot].steer_qstart = h_qstart;
+	c->slot[slot].steer_qrec = h_qrec;
+	c->slot[slot].steer_qoff = h_qoff;
+	c->slot[slot].steer_qlen = h_qlen;
 	return 0;
 }
 
@@ -2186,6 +2346,38 @@ int mosrx_steer_dev(mosrx_ctx *c, const void *d_rec, uint32_t n, int rec_bytes, 
 	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
 }
 
+int mosrx_steer_gather_dev(mosrx_ctx *c, const void *d_rec, const uint32_t *d_off, const uint16_t *d_len, uint32_t n,
+                           int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart, void *d_qrec, uint32_t *d_qoff,
+                           uint16_t *d_qlen, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+	mosrx_sparams sp;
+	if (!c || !d_rec || !d_idx || !d_qstart || !d_qrec || !d_scratch || (rec_bytes != 8 && rec_bytes != 16) ||
+	    (((uintptr_t)d_idx | (uintptr_t)d_qstart | (uintptr_t)d_scratch) & 3) ||
+	    (((uintptr_t)d_rec | (uintptr_t)d_qrec) & (uintptr_t)(rec_bytes - 1)) ||
+	    !d_qoff != !d_qlen || (d_qoff && (!d_off || !d_len)) ||
+	    (d_qoff && ((((uintptr_t)d_qoff | (uintptr_t)d_off) & 3) || (((uintptr_t)d_qlen | (uintptr_t)d_len) & 1))) ||
+	    scratch_bytes < mosrx_steer_scratch_bytes(n))
+		return -EINVAL;
+	if (n == 0)
+		return 0;
+	memset(&sp, 0, sizeof(sp));
+	sp.one.rec = (const uint8_t *)d_rec;
+	sp.one.idx = d_idx;
+	sp.one.qstart = d_qstart;
+	sp.one.n = n;
+	sp.gone.off = d_off;
+	sp.gone.len = d_len;
+	sp.gone.qrec = (uint8_t *)d_qrec;
+	sp.gone.qoff = d_qoff;
+	sp.gone.qlen = d_qlen;
+	sp.gather = 1;
+	sp.hist = (uint32_t *)d_scratch;
+	sp.nb = 1;
+	sp.rec_bytes = (uint32_t)rec_bytes;
+	sp.total_tiles = (n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
+	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
+}
+
 void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 {
 	if (!q)
@@ -2196,6 +2388,8 @@ void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 		hipFree(q->d_desc);
 	if (q->d_sdesc)
 		hipFree(q->d_sdesc);
+	if (q->d_gdesc)
+		hipFree(q->d_gdesc);
 	if (q->d_shist)
 		hipFree(q->d_shist);
 	free(q->h_desc);

@@ -70,6 +70,17 @@ struct slot {
 	uint32_t *const *steer_idx, *const *steer_qstart;
 	mosrx_sdesc *h_sdesc, *d_sdesc;
 	uint32_t *d_sidx, *d_shist, *d_sqstart;
+	/* ... and of its queue-major gather (mosrx_slot_steer_gather): the armed
+	 * outputs (steer_qrec NULL: a plain steer; steer_qoff / steer_qlen NULL:
+	 * records only), the gather table parallel to h_sdesc / d_sdesc, and the
+	 * slot's own records, offsets and lengths for cap_n frames */
+	void *const *steer_qrec;
+	uint32_t *const *steer_qoff;
+	uint16_t *const *steer_qlen;
+	mosrx_gdesc *h_gdesc, *d_gdesc;
+	uint8_t *d_sqrec;
+	uint32_t *d_sqoff;
+	uint16_t *d_sqlen;
 	int timed;
 	int busy;
 };
@@ -120,6 +131,8 @@ struct mosrx_ctx {
 	 * per timing stream and one for the context stream (mosrx_time_op) */
 	uint8_t *steer_tmp;
 	size_t steer_tmp_stride, steer_tmp_bytes;
+	size_t steer_tmp_scratch;        /*   the scratch part of a block, and the frames its gather part holds */
+	uint32_t steer_tmp_n;
 };
 
 int mosrx__check_batch(const mosrx_batch *b, int dev);

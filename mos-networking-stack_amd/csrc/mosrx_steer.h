@@ -29,6 +29,19 @@ typedef struct mosrx_sdesc {
 	uint32_t       tile_base; /* the batch's first histogram row = its first workgroup in the launch */
 } mosrx_sdesc;
 
+/* The queue-major gather of one batch, parallel to its mosrx_sdesc (which
+ * stays 32 bytes): the scatter pass also stores, in the order of idx,
+ *   qrec[j] = rec[idx[j]]   whole records, rec and qrec aligned to rec_bytes
+ *   qoff[j] = off[idx[j]], qlen[j] = len[idx[j]]   both given or both NULL
+ * so queue q's share is three contiguous runs from qstart[q].  40 bytes. */
+typedef struct mosrx_gdesc {
+	const uint32_t *off;      /* the batch's descriptors; read only with qoff / qlen */
+	const uint16_t *len;
+	uint8_t        *qrec;     /* n records of rec_bytes */
+	uint32_t       *qoff;     /* n, or NULL: records only */
+	uint16_t       *qlen;     /* n, or NULL with qoff */
+} mosrx_gdesc;
+
 typedef struct mosrx_sparams {
 	const mosrx_sdesc *desc;  /* nb entries in device-visible memory, or NULL: the one batch in `one` */
 	mosrx_sdesc        one;
@@ -36,10 +49,15 @@ typedef struct mosrx_sparams {
 	uint32_t           nb;
 	uint32_t           rec_bytes;   /* 8 or 16 */
 	uint32_t           total_tiles;
+	uint32_t           gather;      /* 1: the scatter pass is the gather form, over gdesc[] (with desc) or gone */
+	const mosrx_gdesc *gdesc; /* nb entries parallel to desc[], or NULL */
+	mosrx_gdesc        gone;  /* the gather of `one` */
 } mosrx_sparams;
 
 /* The three launches (histogram, scan, scatter) on `stream` (a hipStream_t);
- * 0, -EINVAL or -EIO.  Allocates nothing. */
+ * 0, -EINVAL or -EIO.  Allocates nothing.  gather == 0 is the plain scatter
+ * whatever gdesc / gone hold; with gather the single-batch form's pointers are
+ * checked here (-EINVAL), a table's by whoever filled it. */
 int mosrx_launch_steer(const mosrx_sparams *sp, void *stream);
 
 #ifdef __cplusplus

@@ -20,6 +20,10 @@
 // one ballot per key bit (8 rounds whatever the keys are; peeling distinct
 // keys one ballot each would take up to 64 rounds on a slice of many queues).
 //
+// With gather outputs (mosrx_gdesc) the scatter launch is its gather form
+// (3g below): the same positions, with the frame's record, offset and length
+// stored beside idx[pos].  Launches without them run the plain pass unchanged.
+//
 // The key of frame i is byte rec_bytes - 3 of its record (mosrx_result.queue,
 // mosrx_result8.queue); it is read as the aligned dword that holds it, so a
 // wave's key loads are dword loads at a stride of 8 or 16 bytes: the same
@@ -213,17 +217,143 @@ __global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_scatter_kerne
 	}
 }
 
+// ---- 3g. scatter + queue-major gather ---------------------------------------
+// The scatter pass with the frame's record, offset and length stored at pos
+// next to idx[pos] (mosrx_gdesc).  A lane loads its whole record (one dwordx2
+// or dwordx4: the cache lines the key dword alone touches) and takes the key
+// from it; lanes of one key in a slice get consecutive positions, so each
+// array's stores come in runs.  Same structure as the plain pass: no workgroup
+// waits on another, fixed loop bounds, every store under pos < n.
+template <uint32_t RB> struct steer_rec;
+template <> struct steer_rec<8u> {
+	uint2 v;
+	__device__ __forceinline__ uint32_t key() const { return (v.y >> 8) & 0xFFu; }
+};
+template <> struct steer_rec<16u> {
+	uint4 v;
+	__device__ __forceinline__ uint32_t key() const { return (v.w >> 8) & 0xFFu; }
+};
+
+// steer_batch, and the batch's index in the tables
+__device__ __forceinline__ uint32_t steer_batch_index(const mosrx_sparams &sp, uint32_t blk)
+{
+	uint32_t lo = 0, hi = sp.nb;
+	for (int it = 0; it < 32 && hi - lo > 1; it++) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (sp.desc[mid].tile_base <= blk)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+
+template <uint32_t RB>
+__global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_gather_kernel(mosrx_sparams sp)
+{
+	typedef decltype(steer_rec<RB>::v) vec_t;
+	__shared__ uint32_t s_row[STEER_ROWS][MOSRX_STEER_BINS];
+	const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+	if (blockIdx.x >= sp.total_tiles)
+		return;
+	for (uint32_t j = t; j < STEER_ROWS * MOSRX_STEER_BINS; j += MOSRX_STEER_THREADS)
+		(&s_row[0][0])[j] = 0;
+	__syncthreads();
+	mosrx_sdesc d;
+	mosrx_gdesc g;
+	if (sp.desc) {
+		const uint32_t k = steer_batch_index(sp, blockIdx.x);
+		d = sp.desc[k];
+		g = sp.gdesc[k];
+	} else {
+		d = sp.one;
+		g = sp.gone;
+	}
+	const bool descs = g.qoff != nullptr;   // uniform over the workgroup
+	const uint32_t row0 = wave * STEER_SLICES;
+	const uint32_t first = (blockIdx.x - d.tile_base) * MOSRX_STEER_TILE + row0 * 64u;
+	steer_rec<RB> r[STEER_SLICES];
+	uint32_t key[STEER_SLICES], rank[STEER_SLICES], foff[STEER_SLICES], flen[STEER_SLICES];
+#pragma unroll
+	for (uint32_t s = 0; s < STEER_SLICES; s++) {
+		const uint32_t i = first + s * 64u + lane;
+		const bool valid = i < d.n;
+		r[s].v = vec_t{};
+		foff[s] = flen[s] = 0;
+		if (valid) {
+			r[s].v = *reinterpret_cast<const vec_t *>(d.rec + (uint64_t)i * RB);
+			if (descs) {
+				foff[s] = g.off[i];
+				flen[s] = g.len[i];
+			}
+		}
+		key[s] = valid ? r[s].key() : 0u;
+		const uint64_t same = same_key_mask(key[s], valid);
+		rank[s] = lanes_below(same);
+		if (valid && rank[s] == 0)
+			s_row[row0 + s][key[s]] = (uint32_t)__builtin_popcountll(same);   // one writer per (row, key)
+	}
+	__syncthreads();
+	if (t < MOSRX_STEER_BINS) {
+		uint32_t run = d.qstart[t] + sp.hist[(uint64_t)blockIdx.x * MOSRX_STEER_BINS + t];
+#pragma unroll 8
+		for (uint32_t q = 0; q < STEER_ROWS; q++) {
+			const uint32_t v = s_row[q][t];
+			s_row[q][t] = run;
+			run += v;
+		}
+	}
+	__syncthreads();
+#pragma unroll
+	for (uint32_t s = 0; s < STEER_SLICES; s++) {
+		const uint32_t i = first + s * 64u + lane;
+		if (i < d.n) {
+			const uint32_t pos = s_row[row0 + s][key[s]] + rank[s];
+			if (pos < d.n) {   // as the plain pass: every store of the frame under the one guard
+				d.idx[pos] = i;
+				*reinterpret_cast<vec_t *>(g.qrec + (uint64_t)pos * RB) = r[s].v;
+				if (descs) {
+					g.qoff[pos] = foff[s];
+					g.qlen[pos] = (uint16_t)flen[s];
+				}
+			}
+		}
+	}
+}
+
+static int gather_ok(const mosrx_sparams *sp)
+{
+	const mosrx_gdesc *g = &sp->gone;
+	const uintptr_t rb = sp->rec_bytes;
+	if (sp->desc)
+		return sp->gdesc != NULL;
+	if (!sp->one.n)
+		return 1;
+	if (!g->qrec || (((uintptr_t)sp->one.rec | (uintptr_t)g->qrec) & (rb - 1)) || !g->qoff != !g->qlen)
+		return 0;
+	if (g->qoff && (!g->off || !g->len || (((uintptr_t)g->qoff | (uintptr_t)g->off) & 3) ||
+	                (((uintptr_t)g->qlen | (uintptr_t)g->len) & 1)))
+		return 0;
+	return 1;
+}
+
 extern "C" int mosrx_launch_steer(const mosrx_sparams *sp, void *stream)
 {
 	const hipStream_t s = (hipStream_t)stream;
 	if (!sp || !sp->hist || (sp->rec_bytes != 8u && sp->rec_bytes != 16u) || (sp->desc && sp->nb == 0))
+		return -EINVAL;
+	if (sp->gather && !gather_ok(sp))
 		return -EINVAL;
 	if (sp->total_tiles == 0 && !sp->desc)
 		return 0;
 	if (sp->total_tiles)
 		hipLaunchKernelGGL(mosrx_steer_hist_kernel, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
 	hipLaunchKernelGGL(mosrx_steer_scan_kernel, dim3(sp->desc ? sp->nb : 1u), dim3(SCAN_THREADS), 0, s, *sp);
-	if (sp->total_tiles)
+	if (sp->total_tiles && !sp->gather)
 		hipLaunchKernelGGL(mosrx_steer_scatter_kernel, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
+	else if (sp->total_tiles && sp->rec_bytes == 8u)
+		hipLaunchKernelGGL(mosrx_steer_gather_kernel<8u>, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
+	else if (sp->total_tiles)
+		hipLaunchKernelGGL(mosrx_steer_gather_kernel<16u>, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }

@@ -151,8 +151,10 @@ int mosrx_rx_loop_queues(const io_module_func *iom, struct mtcp_thread_context *
 			const mosrx_result *res = NULL;
 			const mosrx_result8 *res8 = NULL;
 			mosrx_steer_view v;
+			mosrx_queue_view qv;
 			mosrx_result one;
 			uint32_t q, k;
+			int gathered;
 			const int32_t recv_cnt = iom->recv_pkts(ctx, rx_inf);
 			if (recv_cnt < 0) {
 				st->recv_errors++;
@@ -171,9 +173,47 @@ int mosrx_rx_loop_queues(const io_module_func *iom, struct mtcp_thread_context *
 			if (v.n != (uint32_t)recv_cnt || v.qstart[0] != 0 || v.qstart[MOSRX_STEER_QSLOTS - 1] != v.n)
 				return -EIO;
 			memset(&one, 0, sizeof(one));
+			/* a gathering backend (cfg.steer = 2): each queue is read through its
+			 * contiguous view, the same frames in the same order */
+			memset(&qv, 0, sizeof(qv));
+			gathered = iom->dev_ioctl(ctx, rx_inf, MOSRX_PKT_RX_QUEUE, &qv) == 0;
 			for (q = 0; q < MOSRX_STEER_QSLOTS - 1; q++) {
 				if (v.qstart[q] > v.qstart[q + 1] || v.qstart[q + 1] > v.n)
 					return -EIO;
+				if (gathered && v.qstart[q] < v.qstart[q + 1]) {
+					memset(&qv, 0, sizeof(qv));
+					qv.q = q;
+					if (iom->dev_ioctl(ctx, rx_inf, MOSRX_PKT_RX_QUEUE, &qv) || qv.n != v.qstart[q + 1] - v.qstart[q] ||
+					    !qv.rec || !qv.off || !qv.len || !qv.idx || !qv.frames ||
+					    (qv.rec_bytes != sizeof(mosrx_result) && qv.rec_bytes != sizeof(mosrx_result8)))
+						return -EIO;
+					for (k = 0; k < qv.n; k++) {
+						const uint32_t i = qv.idx[k];
+						const uint16_t len = qv.len[k];
+						const uint8_t *pkt = qv.frames + qv.off[k];
+						const mosrx_result *r = (const mosrx_result *)(qv.rec + (size_t)k * qv.rec_bytes);
+						if (i >= v.n)
+							return -EIO;
+						if (qv.rec_bytes == sizeof(mosrx_result8)) {
+							const mosrx_result8 *r8 = (const mosrx_result8 *)(qv.rec + (size_t)k * qv.rec_bytes);
+							one.rss = r8->rss;
+							one.reason = r8->reason;
+							one.queue = r8->queue;
+							one.verdict = r8->verdict;
+							one.tcp_flags = r8->tcp_flags;
+							r = &one;
+						}
+						st->rx_packets++;
+						st->rx_bytes += (uint64_t)len + ETHER_OVR;
+						if (r->verdict < 0)
+							st->rx_errors++;
+						if (r->reason < MOSRX_R_COUNT)
+							st->by_reason[r->reason]++;
+						if (fn && q < nq)
+							fn(arg[q], rx_inf, (int)i, pkt, len, r);
+					}
+					continue;
+				}
 				for (k = v.qstart[q]; k < v.qstart[q + 1]; k++) {
 					const uint32_t i = v.idx[k];
 					uint16_t len = 0;

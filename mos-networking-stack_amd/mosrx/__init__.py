@@ -105,6 +105,7 @@ BPF_LEN_FRAME, BPF_LEN_IP = 0, 1
 TX_IP_CSUM, TX_TCP_CSUM = 1 << 4, 1 << 5   # MOS_UPDATE_IP_CHKSUM / MOS_UPDATE_TCP_CHKSUM
 OP_CLASSIFY, OP_CLASSIFY_FH, OP_BPF, OP_TX_CSUM, OP_CLASSIFY_BPF, OP_CLASSIFY_TI, OP_TX_CHECKS = 0, 1, 2, 3, 4, 5, 6
 OP_STEER = 7           # MOSRX_OP_STEER: the steer sequence over a batch's records (arg = rec_bytes)
+OP_STEER_GATHER = 8    # MOSRX_OP_STEER_GATHER: ... with the scatter launch in its gather form
 STEER_QSLOTS = 257     # MOSRX_STEER_QSLOTS: qstart entries per batch
 # include/mosrx.h mosrx_tx_check: the TX checks of a frame, the frame untouched
 TX_CHECK_DTYPE = np.dtype([("ip_check", "<u2"), ("tcp_check", "<u2"), ("what", "u1"), ("ihl", "u1"),
@@ -142,6 +143,18 @@ class ModuleCfg(C.Structure):
 class SteerView(C.Structure):
     """mosrx_steer_view (dev_ioctl(MOSRX_PKT_RX_STEER))."""
     _fields_ = [("idx", C.c_void_p), ("qstart", C.c_void_p), ("n", C.c_uint32), ("num_queues", C.c_uint32)]
+
+
+class QueueView(C.Structure):
+    """mosrx_queue_view (dev_ioctl(MOSRX_PKT_RX_QUEUE))."""
+    _fields_ = [("q", C.c_uint32), ("n", C.c_uint32), ("rec", C.c_void_p), ("rec_bytes", C.c_uint32),
+                ("off", C.c_void_p), ("len", C.c_void_p), ("idx", C.c_void_p), ("frames", C.c_void_p)]
+
+
+class HubStats(C.Structure):
+    """mosrx_hub_stats."""
+    _fields_ = [("batches", C.c_uint64), ("frames", C.c_uint64), ("delivered", C.c_uint64),
+                ("unowned", C.c_uint64), ("owner_waits", C.c_uint64)]
 
 
 class ModuleStats(C.Structure):
@@ -351,6 +364,15 @@ def lib():
             "mosrx_steer_dev": (I, [P, P, U32, I, P, P, P, C.c_size_t, P]),
             "mosrx_queue_set_steer": (I, [P, P, C.POINTER(P), C.POINTER(P)]),
             "mosrx_slot_steer": (I, [P, I, C.POINTER(P), C.POINTER(P)]),
+            "mosrx_steer_gather_dev": (I, [P, P, P, P, U32, I, P, P, P, P, P, P, C.c_size_t, P]),
+            "mosrx_queue_set_steer_gather": (I, [P, P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P),
+                                                 C.POINTER(P)]),
+            "mosrx_slot_steer_gather": (I, [P, I, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P),
+                                            C.POINTER(P)]),
+            "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
+            "mosrx_hub_endpoint": (P, [P, U32]),
+            "mosrx_hub_stats_get": (I, [P, P]),
+            "mosrx_hub_close": (I, [P]),
             "mosrx_rx_loop_queues": (I, [P, P, I, U32, P, C.POINTER(P), U64, C.POINTER(RxStats)]),
         }
         for name, (res, args) in sig.items():
@@ -854,6 +876,31 @@ class Context:
         self._steer_arm = ((C.c_void_p * len(idx))(*idx), (C.c_void_p * len(qstart))(*qstart))
         _chk(lib().mosrx_slot_steer(self.handle, slot, *self._steer_arm), "mosrx_slot_steer")
 
+    def steer_gather_dev(self, d_rec: int, d_off: int | None, d_len: int | None, n: int, rec_bytes: int, d_idx: int,
+                         d_qstart: int, d_qrec: int, d_qoff: int | None, d_qlen: int | None, d_scratch: int,
+                         scratch_bytes: int, sync: bool = True, stream: int | None = None) -> None:
+        """mosrx_steer_gather_dev: steer_dev, with the records (and, with d_qoff /
+        d_qlen, the batch's offsets and lengths) also stored in the order of idx."""
+        _chk(lib().mosrx_steer_gather_dev(self.handle, d_rec, d_off, d_len, n, rec_bytes, d_idx, d_qstart, d_qrec,
+                                          d_qoff, d_qlen, d_scratch, scratch_bytes, stream),
+             "mosrx_steer_gather_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
+    def slot_steer_gather(self, slot: int, idx: list | None, qstart: list | None = None, qrec: list | None = None,
+                          qoff: list | None = None, qlen: list | None = None) -> None:
+        """mosrx_slot_steer_gather: slot_steer with per-batch gather outputs (host
+        pointers: n records, and n offsets / n lengths or neither); idx None disarms."""
+        if idx is None:
+            self._steer_arm = None
+            _chk(lib().mosrx_slot_steer_gather(self.handle, slot, None, None, None, None, None),
+                 "mosrx_slot_steer_gather")
+            return
+        # the pointer arrays must outlive the submit
+        self._steer_arm = tuple((C.c_void_p * len(a))(*a) if a is not None else None
+                                for a in (idx, qstart, qrec, qoff, qlen))
+        _chk(lib().mosrx_slot_steer_gather(self.handle, slot, *self._steer_arm), "mosrx_slot_steer_gather")
+
     def group_wait(self, slot: int) -> None:
         _chk(lib().mosrx_classify_host_wait(self.handle, slot), "mosrx_classify_host_wait")
 
@@ -897,15 +944,16 @@ class Context:
                 d.d_tinfo = DevBuffer(self, max(d.n * 12, 12))
             if op in (OP_BPF, OP_CLASSIFY_BPF) and d.d_match is None:
                 d.d_match = DevBuffer(self, max(d.n * 4, 4))
-            if op == OP_STEER and d.d_sidx is None:
+            if op in (OP_STEER, OP_STEER_GATHER) and d.d_sidx is None:
                 d.d_sidx = DevBuffer(self, max(d.n * 4, 4))
         bs = (Batch * len(dbs))(*[d.batch() for d in dbs])
         # OP_STEER reads the records a classify call left: the compact ones for arg == 8
         outs = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_BPF else
-                                          d.d_out8.ptr if op == OP_STEER and arg == 8 else d.d_out.ptr) for d in dbs])
+                                          d.d_out8.ptr if op in (OP_STEER, OP_STEER_GATHER) and arg == 8
+                                          else d.d_out.ptr) for d in dbs])
         aux = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_CLASSIFY_BPF else
                                          d.d_tinfo.ptr if op == OP_CLASSIFY_TI else
-                                         d.d_sidx.ptr if op == OP_STEER else
+                                         d.d_sidx.ptr if op in (OP_STEER, OP_STEER_GATHER) else
                                          (d.d_fhash.ptr if d.d_fhash else None)) for d in dbs])
         tot, avg = C.c_float(), C.c_float()
         _chk(lib().mosrx_time_op(self.handle, op, arg, bs, len(dbs), outs, aux, iters, nstreams,
@@ -1021,6 +1069,13 @@ class Queue:
         q = (C.c_void_p * len(qstart))(*qstart)
         _chk(lib().mosrx_queue_set_steer(self.ctx.handle, self.handle, i, q), "mosrx_queue_set_steer")
 
+    def set_steer_gather(self, idx: list | None, qstart: list | None = None, qrec: list | None = None,
+                         qoff: list | None = None, qlen: list | None = None) -> None:
+        """mosrx_queue_set_steer_gather: set_steer with per-batch gather outputs
+        (device pointers: n records, and n offsets / n lengths or neither); idx None detaches."""
+        arrs = [(C.c_void_p * len(a))(*a) if a is not None else None for a in (idx, qstart, qrec, qoff, qlen)]
+        _chk(lib().mosrx_queue_set_steer_gather(self.ctx.handle, self.handle, *arrs), "mosrx_queue_set_steer_gather")
+
     def run(self, sync: bool = True):
         _chk(lib().mosrx_queue_run(self.ctx.handle, self.handle, None), "mosrx_queue_run")
         if sync:
@@ -1086,6 +1141,8 @@ PKT_RX_TCPINFO, PKT_SET_PARAMS = 0x12, 0x13
 PKT_RX_STATE, PKT_RX_RECLASSIFY, PKT_SET_BPF, PKT_RX_FHASH = 0x14, 0x15, 0x16, 0x17
 PKT_RX_RESULTS8 = 0x18
 PKT_RX_STEER = 0x19
+PKT_RX_QUEUE = 0x1A
+QUEUE_PROBE = 0xFFFFFFFF
 
 
 class IoModuleFunc(C.Structure):
@@ -1112,7 +1169,7 @@ class GpuBackend:
                  ngpu: int = 1, bpf=None, group: int = 1, tcpinfo: bool = False, tx_batch: int = 64,
                  timing: bool = False, flowhash: bool = False, tx_csum: bool = False, compact: bool = False,
                  group_bytes: int = 0, group_max_us: int = 0, direct_kb: int | None = None,
-                 direct_frames: int | None = None, module_lib=None, steer: bool = False):
+                 direct_frames: int | None = None, module_lib=None, steer: bool | int = False):
         self.L = L = module_lib or lib()
         cfg = ModuleCfg()
         L.mosrx_gpu_module_cfg_default(C.byref(cfg))
@@ -1131,7 +1188,8 @@ class GpuBackend:
             cfg.direct_kb = direct_kb       # copy-free groups up to this many KiB (0: none)
         if direct_frames is not None:
             cfg.direct_frames = direct_frames   # ... and up to this many frames
-        cfg.steer = int(steer)              # every group steered on the GPU (steer_view, run_loop_queues)
+        cfg.steer = int(steer)              # 1: every group steered on the GPU (steer_view, run_loop_queues);
+        #                                     2: and gathered queue-major (queue_view, Hub)
         if params is not None:
             cfg.params = params
         self.params = Params.from_buffer_copy(cfg.params)
@@ -1208,6 +1266,16 @@ class GpuBackend:
         idx = np.ctypeslib.as_array(C.cast(v.idx, C.POINTER(C.c_uint32)), (max(v.n, 1),))[:v.n].copy()
         qs = np.ctypeslib.as_array(C.cast(v.qstart, C.POINTER(C.c_uint32)), (STEER_QSLOTS,)).copy()
         return idx, qs, int(v.num_queues)
+
+    def queue_view(self, ifidx: int, q: int):
+        """dev_ioctl(MOSRX_PKT_RX_QUEUE): queue q's share of the exposed batch as
+        (rec bytes [n, rec_bytes], off[n], len[n], idx[n], frame base address), or
+        None unless the batch was gathered (cfg.steer = 2)."""
+        v = QueueView()
+        v.q = q
+        if self._ioctl(self.ctx, ifidx, PKT_RX_QUEUE, C.byref(v)):
+            return None
+        return _queue_view_arrays(v)
 
     def run_loop_queues(self, nq: int, fn=None, args: list | None = None, max_rounds: int = 0) -> RxStats:
         """mosrx_rx_loop_queues over this backend: fn (a _PKTFN callback) gets
@@ -1290,6 +1358,62 @@ class GpuBackend:
             for s in self.sources:
                 lib().mosrx_source_close(s)
             self.sources = []
+
+
+def _queue_view_arrays(v: QueueView):
+    n = int(v.n)
+    if n == 0:
+        return (np.zeros((0, int(v.rec_bytes) or 16), np.uint8), np.zeros(0, np.uint32), np.zeros(0, np.uint16),
+                np.zeros(0, np.uint32), v.frames)
+    rec = np.ctypeslib.as_array(C.cast(v.rec, C.POINTER(C.c_uint8)), (n * v.rec_bytes,)).reshape(n, -1).copy()
+    off = np.ctypeslib.as_array(C.cast(v.off, C.POINTER(C.c_uint32)), (n,)).copy()
+    ln = np.ctypeslib.as_array(C.cast(v.len, C.POINTER(C.c_uint16)), (n,)).copy()
+    idx = np.ctypeslib.as_array(C.cast(v.idx, C.POINTER(C.c_uint32)), (n,)).copy()
+    return rec, off, ln, idx, v.frames
+
+
+def hub_module(module_lib=None) -> IoModuleFunc:
+    return IoModuleFunc.in_dll(module_lib or lib(), "mosrx_hub_module_func")
+
+
+class Hub:
+    """mosrx_hub over one gathering backend (an io_module_func address and its
+    context): endpoint(core) is core's context for hub_module().  Open it, and
+    run core 0's endpoint, on the thread that opened the backend."""
+
+    def __init__(self, backend_iom: int, backend_ctx: int | None, nif: int, ncores: int):
+        h = C.c_void_p()
+        _chk(lib().mosrx_hub_open(backend_iom, backend_ctx, nif, ncores, C.byref(h)), "mosrx_hub_open")
+        self.handle, self.nif, self.ncores = h.value, nif, ncores
+        self.m = hub_module()
+        self.iom = C.addressof(self.m)
+
+    def endpoint(self, core: int) -> int:
+        p = lib().mosrx_hub_endpoint(self.handle, core)
+        if not p:
+            raise MosrxError(22, "mosrx_hub_endpoint")
+        return p
+
+    def run_loop(self, core: int, fn=None, arg=None, max_pkts: int = 0) -> tuple[int, RxStats]:
+        """mosrx_rx_loop over core's endpoint (it ends at the first idle round): (rc, stats)."""
+        st = RxStats()
+        rc = lib().mosrx_rx_loop(self.iom, self.endpoint(core), self.nif, max_pkts,
+                                 C.cast(fn, C.c_void_p) if fn is not None else None, arg, C.byref(st))
+        return rc, st
+
+    def stats(self) -> HubStats:
+        st = HubStats()
+        _chk(lib().mosrx_hub_stats_get(self.handle, C.byref(st)), "mosrx_hub_stats_get")
+        return st
+
+    def close(self) -> int:
+        """mosrx_hub_close: 0, or -EBUSY (-16) while a share is outstanding (the hub stays open)."""
+        if not self.handle:
+            return 0
+        rc = lib().mosrx_hub_close(self.handle)
+        if rc == 0:
+            self.handle = None
+        return rc
 
 
 SRC_BEST, SRC_FILL, SRC_PER_FRAME = 0, 1, 2
