@@ -313,6 +313,48 @@ int  mosrx_queue_set_steer_gather(mosrx_ctx *c, mosrx_queue *q, uint32_t *const 
 int  mosrx_slot_steer_gather(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart,
                              void *const *h_qrec, uint32_t *const *h_qoff, uint16_t *const *h_qlen);
 
+/* ---- the gather's side form: a batch's other per-frame outputs in queue order -- */
+/* The gather forms with up to three more arrays stored in the order of idx by
+ * the same launch (its side form; no further launch, histogram and scan as
+ * they are):
+ *   qfhash[j]   = fhash[idx[j]]     the flow-table hashes (u32)
+ *   qmatch[j]   = match[idx[j]]     the BPF match masks (u32)
+ *   qtcpinfo[j] = tcpinfo[idx[j]]   mosrx_tcpinfo, whole
+ * so queue q's hashes, masks and pkt_info are contiguous runs from qstart[q],
+ * beside its records.  Each array on its own: a NULL destination is not
+ * gathered (nothing read, nothing written); with none given the launch is the
+ * plain gather form.  All pointers 4-byte aligned.  Per frame the pass reads
+ * and writes 4 more bytes for a u32 array, 12 for tcpinfo. */
+/* mosrx_steer_gather_dev plus the three source / destination pairs (both
+ * pointers of a pair or neither: -EINVAL otherwise).  Same scratch, allocates
+ * nothing, graph-capturable; n == 0 returns 0 and launches nothing. */
+int  mosrx_steer_gather_side_dev(mosrx_ctx *c, const void *d_rec, const uint32_t *d_off, const uint16_t *d_len,
+                                 uint32_t n, int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart, void *d_qrec,
+                                 uint32_t *d_qoff, uint16_t *d_qlen, const uint32_t *d_fhash, uint32_t *d_qfhash,
+                                 const uint32_t *d_match, uint32_t *d_qmatch, const mosrx_tcpinfo *d_tcpinfo,
+                                 mosrx_tcpinfo *d_qtcpinfo, void *d_scratch, size_t scratch_bytes, void *stream);
+/* mosrx_queue_set_steer_gather plus per-batch d_qfhash / d_qmatch (either may
+ * be NULL); the sources are the queue's own d_fhash / d_match of
+ * mosrx_queue_create_ex, and a destination for an array the queue does not
+ * produce is -EINVAL.  All seven NULL detaches. */
+int  mosrx_queue_set_steer_gather_side(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx,
+                                       uint32_t *const *d_qstart, void *const *d_qrec, uint32_t *const *d_qoff,
+                                       uint16_t *const *d_qlen, uint32_t *const *d_qfhash,
+                                       uint32_t *const *d_qmatch);
+/* mosrx_slot_steer_gather plus h_qfhash / h_qmatch / h_qtcpinfo (any may be
+ * NULL), under its rules.  The armed submit gathers each side array it makes
+ * itself for which a destination was given -- flow hashes with h_fhash, masks
+ * on the _bpf / _bpf_c8 submits, pkt_info with h_tcpinfo -- and leaves the
+ * other destinations untouched.  The slot's buffers for them are part of
+ * mosrx_classify_host_reserve.  All eight NULL disarms. */
+int  mosrx_slot_steer_gather_side(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart,
+                                  void *const *h_qrec, uint32_t *const *h_qoff, uint16_t *const *h_qlen,
+                                  uint32_t *const *h_qfhash, uint32_t *const *h_qmatch,
+                                  mosrx_tcpinfo *const *h_qtcpinfo);
+#define MOSRX_SIDE_FHASH   1   /* the side arrays, as bits (MOSRX_OP_STEER_GATHER_SIDE's arg) */
+#define MOSRX_SIDE_MATCH   2
+#define MOSRX_SIDE_TCPINFO 4
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned
@@ -472,7 +514,10 @@ enum { MOSRX_OP_CLASSIFY = 0, MOSRX_OP_CLASSIFY_FH = 1, MOSRX_OP_BPF = 2, MOSRX_
                            * aux[i] its idx array, `arg` = rec_bytes (8 or 16); qstart and scratch are the
                            * timing call's own.  Three launches: -ENOTSUP from mosrx_time_op_dispatch */,
        MOSRX_OP_STEER_GATHER = 8 /* MOSRX_OP_STEER with the scatter launch in its gather form: the batch's off / len
-                                  * (device resident) are gathered too, into outputs of the timing call's own */ };
+                                  * (device resident) are gathered too, into outputs of the timing call's own */,
+       MOSRX_OP_STEER_GATHER_SIDE = 9 /* MOSRX_OP_STEER_GATHER in its side form: `arg` = rec_bytes | which << 8, which
+                                       * the MOSRX_SIDE_* arrays to gather (0: all three); side sources and outputs
+                                       * are the timing call's own */ };
 int  mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t nb, void *const *out,
                    void *const *aux, uint32_t iters, uint32_t nstreams, float *total_ms, float *avg_kernel_ms);
 /* The kernel's own duration, averaged over `iters` back-to-back launches on

@@ -108,6 +108,17 @@ typedef struct mosrx_queue_view {
 	const uint8_t *frames;       /* the batch's frame base */
 } mosrx_queue_view;
 #define MOSRX_QUEUE_PROBE 0xFFFFFFFFu   /* q: only ask whether the backend gathers (0 / -1; no batch needed, n = 0) */
+#define MOSRX_PKT_RX_QUEUE_SIDE 0x1B /* argp: mosrx_queue_side * -- queue `q`'s share of the exposed batch's other
+                                     * per-frame outputs, as contiguous runs beside MOSRX_PKT_RX_QUEUE's
+                                     * (cfg.steer = 3: the steer pass also gathered them); -1 unless the batch
+                                     * was gathered so.  q = MOSRX_QUEUE_PROBE: only whether the backend does */
+typedef struct mosrx_queue_side {
+	uint32_t q;                  /* in: the queue, or MOSRX_QUEUE_PROBE */
+	uint32_t n;                  /* out: its frames; the arrays below start at qstart[q], frame j as in mosrx_queue_view */
+	const uint32_t *fhash;       /* n flow-table hashes, NULL where MOSRX_PKT_RX_FHASH has none */
+	const uint32_t *match;       /* n BPF match masks, NULL where MOSRX_PKT_RX_MATCH has none */
+	const mosrx_tcpinfo *tcpinfo; /* n pkt_info records, NULL where MOSRX_PKT_RX_TCPINFO has none */
+} mosrx_queue_side;
 typedef struct mosrx_rx_state {
 	uint32_t num_msp, num_esp;   /* the stack state of the batch's verdicts */
 	uint32_t gen;                /* the netdev's parameter / filter generation they were made with */
@@ -263,6 +274,10 @@ typedef struct mosrx_gpu_module_cfg {
 	                                                 * a lone batch then takes the group path.  2: ... and
 	                                                 * gathered queue-major (records, offsets, lengths in the
 	                                                 * order of idx: dev_ioctl(MOSRX_PKT_RX_QUEUE), the hub).
+	                                                 * 3: ... and with them the side arrays the backend makes
+	                                                 * (cfg.flowhash, an installed BPF set, cfg.tcpinfo:
+	                                                 * dev_ioctl(MOSRX_PKT_RX_QUEUE_SIDE); an endpoint of the
+	                                                 * hub then answers RX_FHASH / RX_MATCH / RX_TCPINFO).
 	                                                 * Default 0 */
 } mosrx_gpu_module_cfg;
 #define MOSRX_GROUP_AUTO        0
@@ -405,8 +420,15 @@ int mosrx_rx_loop_queues(const io_module_func *iom, struct mtcp_thread_context *
  * get_rptr(i) the share's i-th frame, and dev_ioctl its records
  * (MOSRX_PKT_RX_RESULTS / RX_RESULTS8: the contiguous gathered run),
  * MOSRX_PKT_RX_STATE, and MOSRX_PKT_RX_QUEUE (the share's own view: idx[i] is
- * frame i's index in the backend's batch).  mosrx_rx_loop runs over an
- * endpoint unchanged.  Two rules:
+ * frame i's index in the backend's batch).  Over a cfg.steer = 3 backend an
+ * endpoint also answers MOSRX_PKT_RX_MATCH, MOSRX_PKT_RX_FHASH and
+ * MOSRX_PKT_RX_TCPINFO with the share's own contiguous run (indexed like
+ * get_rptr; -1 for an array the batch does not have) and
+ * MOSRX_PKT_RX_QUEUE_SIDE with the share's side view, so the mOS consumer
+ * (mosrx_mos_process_packet) finds the GPU's masks and hashes through an
+ * endpoint; over cfg.steer = 2 they stay -1.  Control ioctls (SET_PARAMS,
+ * SET_BPF, RX_RECLASSIFY) are -1 from every endpoint.  mosrx_rx_loop runs over
+ * an endpoint unchanged.  Two rules:
  *   - only the owner calls the backend: core 0's endpoint, on the thread that
  *     opened the hub (which must be the thread that opened the backend); no
  *     backend or HIP call is made from another core's thread.  The owner's

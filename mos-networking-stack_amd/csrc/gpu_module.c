@@ -79,6 +79,9 @@ struct stage {
 	uint32_t *qoff;           /*   their offsets */
 	uint16_t *qlen;           /*   and lengths */
 	int gathered;             /* its last launch filled them (MOSRX_PKT_RX_QUEUE) */
+	uint32_t *qfh, *qmt;      /* pinned, the gather's side arrays (cfg.steer = 3): fh / match in the order of sidx */
+	mosrx_tcpinfo *qti;       /*   and ti; each NULL when its last launch did not gather it (MOSRX_PKT_RX_QUEUE_SIDE) */
+	int sided;                /* its last launch was armed with them */
 	uint32_t n, max_len;
 	uint32_t rec0;            /* its first record's index in the group's record arrays */
 	uint32_t stride;          /* frame i at off[0] + i * stride (a fixed-size packing), else 0: the layout hint */
@@ -108,6 +111,8 @@ struct group {
 	uint8_t *sqrec;           /* cfg.steer = 2: rec_cap gathered records (16-byte slots), */
 	uint32_t *sqoff;          /*   offsets */
 	uint16_t *sqlen;          /*   and lengths */
+	uint32_t *sqfh, *sqmt;    /* cfg.steer = 3: rec_cap gathered flow hashes / match masks, */
+	mosrx_tcpinfo *sqti;      /*   and pkt_info; each only with the array it follows (fh, match, ti) */
 	uint64_t rec_cap;         /* frames the record arrays hold */
 	struct stage *st;         /* cap_st stages */
 	uint32_t cap_st;
@@ -427,6 +432,9 @@ static void group_free(mosrx_ctx *mc, struct group *g)
 	if (g->sqrec) mosrx_host_free(mc, g->sqrec);
 	if (g->sqoff) mosrx_host_free(mc, g->sqoff);
 	if (g->sqlen) mosrx_host_free(mc, g->sqlen);
+	if (g->sqfh) mosrx_host_free(mc, g->sqfh);
+	if (g->sqmt) mosrx_host_free(mc, g->sqmt);
+	if (g->sqti) mosrx_host_free(mc, g->sqti);
 	free(g->st);
 	memset(g, 0, sizeof(*g));
 }
@@ -499,9 +507,13 @@ static int group_alloc_sized(mosrx_ctx *mc, struct group *g, uint64_t bytes)
 	    (g_cfg.flowhash && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->fh)) ||
 	    (g_cfg.steer && (mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sidx) ||
 	                     mosrx_host_alloc(mc, (size_t)g->cap_st * MOSRX_STEER_QSLOTS * 4, (void **)&g->sqs))) ||
-	    (g_cfg.steer == 2 && (mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_result), (void **)&g->sqrec) ||
+	    (g_cfg.steer >= 2 && (mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_result), (void **)&g->sqrec) ||
 	                          mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sqoff) ||
-	                          mosrx_host_alloc(mc, g->rec_cap * 2, (void **)&g->sqlen))))
+	                          mosrx_host_alloc(mc, g->rec_cap * 2, (void **)&g->sqlen))) ||
+	    (g_cfg.steer == 3 &&
+	     ((g_cfg.flowhash && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sqfh)) ||
+	      (MATCH_UP_FRONT && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sqmt)) ||
+	      (g_cfg.tcpinfo && mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_tcpinfo), (void **)&g->sqti)))))
 		return -ENOMEM;
 	return 0;
 }
@@ -744,7 +756,7 @@ static void group_fill(struct if_state *is, struct group *g)
 		s->steered = 0;
 		s->qoff = g->sqoff ? g->sqoff + recs : NULL;
 		s->qlen = g->sqlen ? g->sqlen + recs : NULL;
-		s->gathered = 0;
+		s->gathered = s->sided = 0;
 		if (!s->n)
 			break;
 		g->nst++;
@@ -825,7 +837,13 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	void *gr[MOSRX_MAX_GROUP];
 	uint32_t *go[MOSRX_MAX_GROUP];
 	uint16_t *gl[MOSRX_MAX_GROUP];
-	const int gather = g_cfg.steer == 2 && g->sqrec;
+	uint32_t *gf[MOSRX_MAX_GROUP], *gm[MOSRX_MAX_GROUP];
+	mosrx_tcpinfo *gt[MOSRX_MAX_GROUP];
+	const int gather = g_cfg.steer >= 2 && g->sqrec;
+	/* cfg.steer = 3: the side arrays this submit makes are gathered with the records */
+	const int side = gather && g_cfg.steer == 3;
+	const int side_fh = side && g_cfg.flowhash && g->sqfh, side_mt = side && is->nprog && g->sqmt;
+	const int side_ti = side && g_cfg.tcpinfo && !g_cfg.compact && !is->nprog && g->sqti;
 	uint32_t i, nb = g->nst - first;
 	int rc;
 	if (follow_mos_state(pv, is))
@@ -850,6 +868,10 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 		go[i - first] = s->qoff;
 		gl[i - first] = s->qlen;
 		s->gathered = s->steered && gather;
+		gf[i - first] = s->qfh = side_fh ? g->sqfh + s->rec0 : NULL;
+		gm[i - first] = s->qmt = side_mt ? g->sqmt + s->rec0 : NULL;
+		gt[i - first] = s->qti = side_ti ? g->sqti + s->rec0 : NULL;
+		s->sided = s->gathered && side;
 		s->msp = is->params.num_msp;
 		s->esp = is->params.num_esp;
 		s->gen = is->gen;
@@ -860,8 +882,10 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	}
 	/* cfg.steer: every group is armed (the submit below takes the arm; sx / sq
 	 * are read before it returns) */
-	if (g_cfg.steer && (gather ? mosrx_slot_steer_gather(is->mc, k, sx, sq, gr, go, gl)
-	                           : mosrx_slot_steer(is->mc, k, sx, sq)))
+	if (g_cfg.steer && (side     ? mosrx_slot_steer_gather_side(is->mc, k, sx, sq, gr, go, gl, side_fh ? gf : NULL,
+	                                                            side_mt ? gm : NULL, side_ti ? gt : NULL)
+	                    : gather ? mosrx_slot_steer_gather(is->mc, k, sx, sq, gr, go, gl)
+	                             : mosrx_slot_steer(is->mc, k, sx, sq)))
 		return -1;
 	if (compact && is->nprog)   /* 8-byte records + the set's masks: the fused kernel's 8-byte form */
 		rc = mosrx_classify_host_group_submit_bpf_c8(is->mc, k, b, nb, out8, g_cfg.flowhash ? fh : NULL, mt);
@@ -1175,6 +1199,8 @@ static int32_t set_bpf(struct gpu_priv *pv, struct if_state *is, const mosrx_bpf
 			return -1;
 		for (i = 0; i < g->nst; i++)
 			g->st[i].match = g->match + g->st[i].rec0;
+		if (g_cfg.steer == 3 && !g->sqmt && mosrx_host_alloc(is->mc, g->rec_cap * 4, (void **)&g->sqmt))
+			return -1;
 	}
 	is->nprog = a->nprog;
 	is->gen++;
@@ -1232,7 +1258,7 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 		if (v->q == MOSRX_QUEUE_PROBE) {   /* does this backend gather at all (no batch needed) */
 			memset(v, 0, sizeof(*v));
 			v->q = MOSRX_QUEUE_PROBE;
-			return g_cfg.steer == 2 ? 0 : -1;
+			return g_cfg.steer >= 2 ? 0 : -1;
 		}
 		if (!s || !s->steered || !s->gathered || !v || v->q >= MOSRX_STEER_QSLOTS - 1)
 			return -1;
@@ -1247,6 +1273,27 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 		v->len = s->qlen + q0;
 		v->idx = s->sidx + q0;
 		v->frames = s->frames;
+		return 0;
+	}
+	case MOSRX_PKT_RX_QUEUE_SIDE: {
+		mosrx_queue_side *v = argp;
+		uint32_t q0, q1;
+		if (v->q == MOSRX_QUEUE_PROBE) {   /* does this backend gather side arrays at all */
+			memset(v, 0, sizeof(*v));
+			v->q = MOSRX_QUEUE_PROBE;
+			return g_cfg.steer == 3 ? 0 : -1;
+		}
+		if (!s || !s->steered || !s->gathered || !s->sided || v->q >= MOSRX_STEER_QSLOTS - 1)
+			return -1;
+		q0 = s->sqs[v->q];
+		q1 = s->sqs[v->q + 1];
+		if (q0 > q1 || q1 > s->n)
+			return -1;
+		v->n = q1 - q0;
+		/* an array the batch has (as RX_FHASH / RX_MATCH / RX_TCPINFO answer) and its last launch gathered */
+		v->fhash = s->has_fh && s->qfh ? s->qfh + q0 : NULL;
+		v->match = s->match && s->nprog && s->qmt ? s->qmt + q0 : NULL;
+		v->tcpinfo = s->has_ti && s->qti ? s->qti + q0 : NULL;
 		return 0;
 	}
 	case MOSRX_PKT_RX_TCPINFO:

@@ -1,9 +1,11 @@
 /*
  * hub.c — one steering backend, one io_module endpoint per mTCP core.
  *
- * The backend (opened with cfg.steer = 2) exposes one batch at a time, sorted
- * and gathered by queue on the GPU (MOSRX_PKT_RX_QUEUE: queue q's records,
- * offsets, lengths and original indices as contiguous runs).  The hub hands
+ * The backend (opened with cfg.steer = 2 or 3) exposes one batch at a time,
+ * sorted and gathered by queue on the GPU (MOSRX_PKT_RX_QUEUE: queue q's
+ * records, offsets, lengths and original indices as contiguous runs; with
+ * cfg.steer = 3 also MOSRX_PKT_RX_QUEUE_SIDE: its flow hashes, match masks and
+ * pkt_info).  The hub hands
  * queue q's run to core q's recv_pkts, the ring an RSS NIC would have filled
  * for that core (core.c:1369-1466 runs one mTCP thread per core, each calling
  * its own recv_pkts).
@@ -37,6 +39,7 @@
  * before the epoch's release store, read by that core after its acquire load. */
 struct hub_share {
 	mosrx_queue_view v;
+	mosrx_queue_side side;       /* all NULL: the backend gathers no side arrays, or the batch has none */
 	mosrx_rx_state state;
 	int has_state;
 };
@@ -67,6 +70,7 @@ struct mosrx_hub {
 	int nif;
 	uint32_t ncores;
 	pthread_t owner;
+	int side;                    /* every netdev of the backend answers MOSRX_PKT_RX_QUEUE_SIDE (cfg.steer = 3) */
 	struct hub_if *ifs;          /* nif */
 	struct hub_endpoint *ep;     /* ncores */
 	mosrx_hub_stats stats;       /* the owner's */
@@ -101,6 +105,12 @@ static int32_t hub_pump(struct mosrx_hub *h, int ifidx)
 		if (h->be->dev_ioctl(h->be_ctx, ifidx, MOSRX_PKT_RX_QUEUE, &s->v) || s->v.n > (uint32_t)n ||
 		    (s->v.n && (!s->v.rec || !s->v.off || !s->v.len || !s->v.idx || !s->v.frames)))
 			return -1;   /* not a gathered batch: nothing is published, the next call moves on */
+		/* its side arrays: on this thread too; a batch gathered without them leaves the share's pointers NULL */
+		s->side.q = q;
+		if (!h->side || h->be->dev_ioctl(h->be_ctx, ifidx, MOSRX_PKT_RX_QUEUE_SIDE, &s->side) || s->side.n != s->v.n)
+			memset(&s->side, 0, sizeof(s->side));
+		s->side.q = q;
+		s->side.n = s->v.n;
 		s->state = state;
 		s->state.n = s->v.n;
 		s->state.rec_bytes = s->v.rec_bytes;
@@ -216,6 +226,27 @@ static int32_t hub_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 	case MOSRX_PKT_RX_QUEUE:     /* the share's own view, whatever q asks */
 		*(mosrx_queue_view *)argp = s->v;
 		return 0;
+	/* the share's runs of the batch's side arrays (frame i of the share at [i], as get_rptr(i)) */
+	case MOSRX_PKT_RX_MATCH:
+		if (!s->side.match)
+			return -1;
+		*(const uint32_t **)argp = s->side.match;
+		return 0;
+	case MOSRX_PKT_RX_FHASH:
+		if (!s->side.fhash)
+			return -1;
+		*(const uint32_t **)argp = s->side.fhash;
+		return 0;
+	case MOSRX_PKT_RX_TCPINFO:
+		if (!s->side.tcpinfo)
+			return -1;
+		*(const mosrx_tcpinfo **)argp = s->side.tcpinfo;
+		return 0;
+	case MOSRX_PKT_RX_QUEUE_SIDE:
+		if (!e->hub->side)
+			return -1;
+		*(mosrx_queue_side *)argp = s->side;
+		return 0;
 	default:
 		return -1;
 	}
@@ -233,8 +264,9 @@ int mosrx_hub_open(const io_module_func *backend, struct mtcp_thread_context *ba
 {
 	struct mosrx_hub *h;
 	mosrx_queue_view probe;
+	mosrx_queue_side sprobe;
 	uint32_t q;
-	int i;
+	int i, side = 1;
 	if (out)
 		*out = NULL;
 	if (!backend || !backend->recv_pkts || !out || nif <= 0 || nif > MOSRX_MAX_DEVICES || ncores == 0 ||
@@ -247,6 +279,10 @@ int mosrx_hub_open(const io_module_func *backend, struct mtcp_thread_context *ba
 		probe.q = MOSRX_QUEUE_PROBE;
 		if (backend->dev_ioctl(backend_ctx, i, MOSRX_PKT_RX_QUEUE, &probe))
 			return -ENOTSUP;
+		memset(&sprobe, 0, sizeof(sprobe));
+		sprobe.q = MOSRX_QUEUE_PROBE;
+		if (backend->dev_ioctl(backend_ctx, i, MOSRX_PKT_RX_QUEUE_SIDE, &sprobe))
+			side = 0;   /* a cfg.steer = 2 backend: records and descriptors only, as before */
 	}
 	if (!(h = calloc(1, sizeof(*h))))
 		return -ENOMEM;
@@ -255,6 +291,7 @@ int mosrx_hub_open(const io_module_func *backend, struct mtcp_thread_context *ba
 	h->nif = nif;
 	h->ncores = ncores;
 	h->owner = pthread_self();
+	h->side = side;
 	if (posix_memalign((void **)&h->ifs, 64, (size_t)nif * sizeof(*h->ifs)))
 		h->ifs = NULL;
 	if (posix_memalign((void **)&h->ep, 64, (size_t)ncores * sizeof(*h->ep)))

@@ -207,6 +207,9 @@ int mosrx_open(int device, const mosrx_params *p, mosrx_ctx **out)
 		    hipMalloc((void **)&c->slot[i].d_gdesc, MOSRX_MAX_GROUP * sizeof(mosrx_gdesc)) != hipSuccess ||
 		    hipHostMalloc((void **)&c->slot[i].h_gdesc, MOSRX_MAX_GROUP * sizeof(mosrx_gdesc),
 		                  hipHostMallocDefault) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_xdesc, MOSRX_MAX_GROUP * sizeof(mosrx_xdesc)) != hipSuccess ||
+		    hipHostMalloc((void **)&c->slot[i].h_xdesc, MOSRX_MAX_GROUP * sizeof(mosrx_xdesc),
+		                  hipHostMallocDefault) != hipSuccess ||
 		    hipMalloc((void **)&c->slot[i].d_cnt, MOSRX_CNT_WORDS * 4) != hipSuccess ||
 		    hipHostMalloc((void **)&c->slot[i].h_cnt, MOSRX_CNT_WORDS * 4, hipHostMallocDefault) != hipSuccess ||
 		    !(c->slot[i].h_prev = calloc(MOSRX_CNT_WORDS, 4))) {
@@ -242,6 +245,10 @@ static void slot_free(struct slot *s)
 	if (s->d_sqrec) hipFree(s->d_sqrec);
 	if (s->d_sqoff) hipFree(s->d_sqoff);
 	if (s->d_sqlen) hipFree(s->d_sqlen);
+	if (s->d_sqfh) hipFree(s->d_sqfh);
+	if (s->d_sqmt) hipFree(s->d_sqmt);
+	if (s->d_sqti) hipFree(s->d_sqti);
+	s->d_sqfh = NULL; s->d_sqmt = NULL; s->d_sqti = NULL;
 	s->d_sidx = NULL; s->d_shist = NULL;
 	s->d_sqrec = NULL; s->d_sqoff = NULL; s->d_sqlen = NULL;
 	s->d_frames = NULL; s->d_off = NULL; s->d_len = NULL; s->d_res = NULL; s->d_fh = NULL; s->d_ti = NULL;
@@ -279,6 +286,8 @@ void mosrx_close(mosrx_ctx *c)
 		if (c->slot[i].d_sqstart) hipFree(c->slot[i].d_sqstart);
 		if (c->slot[i].d_gdesc) hipFree(c->slot[i].d_gdesc);
 		if (c->slot[i].h_gdesc) hipHostFree(c->slot[i].h_gdesc);
+		if (c->slot[i].d_xdesc) hipFree(c->slot[i].d_xdesc);
+		if (c->slot[i].h_xdesc) hipHostFree(c->slot[i].h_xdesc);
 		if (c->slot[i].d_cnt) hipFree(c->slot[i].d_cnt);
 		if (c->slot[i].h_cnt) hipHostFree(c->slot[i].h_cnt);
 		free(c->slot[i].h_prev);
@@ -655,7 +664,10 @@ int mosrx__slot_reserve(mosrx_ctx *c, struct slot *s, uint64_t frames_bytes, uin
 		    hipMalloc((void **)&s->d_shist, steer_group_scratch(nn)) != hipSuccess ||
 		    hipMalloc((void **)&s->d_sqrec, (size_t)nn * sizeof(mosrx_result)) != hipSuccess ||
 		    hipMalloc((void **)&s->d_sqoff, (size_t)nn * 4) != hipSuccess ||
-		    hipMalloc((void **)&s->d_sqlen, (size_t)nn * 2) != hipSuccess) {
+		    hipMalloc((void **)&s->d_sqlen, (size_t)nn * 2) != hipSuccess ||
+		    hipMalloc((void **)&s->d_sqfh, (size_t)nn * 4) != hipSuccess ||
+		    hipMalloc((void **)&s->d_sqmt, (size_t)nn * 4) != hipSuccess ||
+		    hipMalloc((void **)&s->d_sqti, (size_t)nn * sizeof(mosrx_tcpinfo)) != hipSuccess) {
 			slot_free(s);
 			return -ENOMEM;
 		}
@@ -1056,7 +1068,32 @@ struct gather_out {
 	void *const *qrec;          /* NULL: a plain steer */
 	uint32_t *const *qoff;      /* NULL with qlen: records only */
 	uint16_t *const *qlen;
+	/* its side form (mosrx_slot_steer_gather_side): the destinations this
+	 * submit gathers (each NULL: not armed, or the submit does not make the
+	 * array), and where the group's launches wrote batch i's masks when they
+	 * are not in the batch table (match_src; the per-batch BPF fallback) */
+	uint32_t *const *qfhash, *const *qmatch;
+	mosrx_tcpinfo *const *qtcpinfo;
+	const uint32_t **match_src;
 };
+#define GATHER_SIDE(g) ((g)->qfhash || (g)->qmatch || (g)->qtcpinfo)
+
+/* ... and for its side outputs, into the slot's side table xd[]. */
+static int side_outputs(int device, const mosrx_batch *b, uint32_t nb, const struct gather_out *g, mosrx_xdesc *xd)
+{
+	uint32_t i;
+	for (i = 0; i < nb; i++) {
+		memset(&xd[i], 0, sizeof(xd[i]));
+		if (!b[i].n)
+			continue;
+		if ((g->qfhash && !(xd[i].qfhash = mosrx__host_dev_of(g->qfhash[i], (uint64_t)b[i].n * 4, device))) ||
+		    (g->qmatch && !(xd[i].qmatch = mosrx__host_dev_of(g->qmatch[i], (uint64_t)b[i].n * 4, device))) ||
+		    (g->qtcpinfo && !(xd[i].qtcpinfo = mosrx__host_dev_of(g->qtcpinfo[i],
+		                                                          (uint64_t)b[i].n * sizeof(mosrx_tcpinfo), device))))
+			return 0;
+	}
+	return 1;
+}
 
 /* ... and for its gather outputs, into the slot's gather table gd[]. */
 static int gather_outputs(int device, const mosrx_batch *b, uint32_t nb, size_t rsz, const struct gather_out *g,
@@ -1083,7 +1120,8 @@ static int gather_outputs(int device, const mosrx_batch *b, uint32_t nb, size_t 
  * or the slot's buffers, which are then copied back -- one copy per run of
  * batches whose host arrays follow each other.  With gather outputs armed
  * (g->qrec) the scatter pass is its gather form, over the descriptors where
- * the classify launch read them. */
+ * the classify launch read them; with side outputs its side form, over the
+ * side arrays where the group's launches wrote them. */
 static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
                        uint32_t *const *h_idx, uint32_t *const *h_qstart, const struct gather_out *g)
 {
@@ -1112,12 +1150,28 @@ static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t
 			gd->off = s->h_qdesc[i].off;
 			gd->len = s->h_qdesc[i].len;
 		}
+		if (GATHER_SIDE(g)) {
+			mosrx_xdesc *xd = &s->h_xdesc[i];
+			if (!in_place) {
+				xd->qfhash = b[i].n && g->qfhash ? s->d_sqfh + pre : NULL;
+				xd->qmatch = b[i].n && g->qmatch ? s->d_sqmt + pre : NULL;
+				xd->qtcpinfo = b[i].n && g->qtcpinfo ? s->d_sqti + pre : NULL;
+			}
+			xd->fhash = xd->qfhash ? s->h_qdesc[i].fhash : NULL;
+			xd->match = !xd->qmatch ? NULL : g->match_src ? g->match_src[i] : s->h_qdesc[i].bmatch;
+			xd->tcpinfo = xd->qtcpinfo ? s->h_qdesc[i].tinfo : NULL;
+		}
 	}
 	HIPCHK(hipMemcpyAsync(s->d_sdesc, s->h_sdesc, nb * sizeof(mosrx_sdesc), hipMemcpyHostToDevice, s->stream));
 	if (g->qrec) {
 		HIPCHK(hipMemcpyAsync(s->d_gdesc, s->h_gdesc, nb * sizeof(mosrx_gdesc), hipMemcpyHostToDevice, s->stream));
 		sp.gdesc = s->d_gdesc;
 		sp.gather = 1;
+	}
+	if (GATHER_SIDE(g)) {
+		HIPCHK(hipMemcpyAsync(s->d_xdesc, s->h_xdesc, nb * sizeof(mosrx_xdesc), hipMemcpyHostToDevice, s->stream));
+		sp.xdesc = s->d_xdesc;
+		sp.side = 1;
 	}
 	sp.desc = s->d_sdesc;
 	sp.hist = s->d_shist;
@@ -1135,6 +1189,13 @@ static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t
 			HIPCHK(hipMemcpyAsync(g->qoff[i], s->d_sqoff + pre, (size_t)b[i].n * 4, hipMemcpyDeviceToHost, s->stream));
 			HIPCHK(hipMemcpyAsync(g->qlen[i], s->d_sqlen + pre, (size_t)b[i].n * 2, hipMemcpyDeviceToHost, s->stream));
 		}
+		if (g->qfhash)
+			HIPCHK(hipMemcpyAsync(g->qfhash[i], s->d_sqfh + pre, (size_t)b[i].n * 4, hipMemcpyDeviceToHost, s->stream));
+		if (g->qmatch)
+			HIPCHK(hipMemcpyAsync(g->qmatch[i], s->d_sqmt + pre, (size_t)b[i].n * 4, hipMemcpyDeviceToHost, s->stream));
+		if (g->qtcpinfo)
+			HIPCHK(hipMemcpyAsync(g->qtcpinfo[i], s->d_sqti + pre, (size_t)b[i].n * sizeof(mosrx_tcpinfo),
+			                      hipMemcpyDeviceToHost, s->stream));
 	}
 	for (i = 0, pre = 0; !in_place && i < nb;) {
 		uint32_t j = i + 1;
@@ -1179,6 +1240,7 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	int fused = 0, uni = 0, direct, out_direct;
 	uint32_t *const *h_sidx, *const *h_sqs;
 	struct gather_out go;
+	const uint32_t *msrc[MOSRX_MAX_GROUP];
 	if (!c || slot < 0 || slot >= NSLOT || !b || !h_out || nb == 0 || nb > MOSRX_MAX_GROUP ||
 	    (h_match && h_tcpinfo) || (compact && h_tcpinfo))
 		return -EINVAL;
@@ -1188,7 +1250,11 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	/* mosrx_slot_steer armed this submit, whatever becomes of it */
 	h_sidx = s->steer_idx;
 	h_sqs = s->steer_qstart;
-	go = (struct gather_out){s->steer_qrec, s->steer_qoff, s->steer_qlen};
+	/* (the side arrays this submit does not make are not gathered: their destinations stay as they are) */
+	go = (struct gather_out){s->steer_qrec, s->steer_qoff, s->steer_qlen, h_fhash ? s->steer_qfhash : NULL,
+	                         h_match ? s->steer_qmatch : NULL, h_tcpinfo ? s->steer_qtcpinfo : NULL, NULL};
+	s->steer_qfhash = s->steer_qmatch = NULL;
+	s->steer_qtcpinfo = NULL;
 	s->steer_idx = s->steer_qstart = NULL;
 	s->steer_qrec = NULL;
 	s->steer_qoff = NULL;
@@ -1201,7 +1267,10 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 		               (h_sidx && (!h_sidx[i] || !h_sqs[i] || (((uintptr_t)h_sidx[i] | (uintptr_t)h_sqs[i]) & 3))) ||
 		               (go.qrec && (!go.qrec[i] || ((uintptr_t)go.qrec[i] & (rsz - 1)))) ||
 		               (go.qoff && (!go.qoff[i] || !go.qlen[i] || ((uintptr_t)go.qoff[i] & 3) ||
-		                            ((uintptr_t)go.qlen[i] & 1)))))
+		                            ((uintptr_t)go.qlen[i] & 1))) ||
+		               (go.qfhash && (!go.qfhash[i] || ((uintptr_t)go.qfhash[i] & 3))) ||
+		               (go.qmatch && (!go.qmatch[i] || ((uintptr_t)go.qmatch[i] & 3))) ||
+		               (go.qtcpinfo && (!go.qtcpinfo[i] || ((uintptr_t)go.qtcpinfo[i] & 3)))))
 			return -EINVAL;
 		if (!b[i].max_len)
 			unknown = 1;
@@ -1225,7 +1294,8 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	direct = direct_regions(c, s, r, nr, ntot, &dev_bytes);
 	out_direct = direct && direct_outputs(c->device, b, nb, h_out, rsz, h_tcpinfo, h_fhash, h_match, od) &&
 	             (!h_sidx || steer_outputs(c->device, b, nb, h_sidx, h_sqs, s->h_sdesc)) &&
-	             (!go.qrec || gather_outputs(c->device, b, nb, rsz, &go, s->h_gdesc));
+	             (!go.qrec || gather_outputs(c->device, b, nb, rsz, &go, s->h_gdesc)) &&
+	             (!GATHER_SIDE(&go) || side_outputs(c->device, b, nb, &go, s->h_xdesc));
 	if (!direct) {
 		group_copy(s, r, nr, &dev_bytes, 0);
 		if ((rc = mosrx__slot_reserve(c, s, dev_bytes, ntot)))
@@ -1303,12 +1373,14 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	} else {
 		if ((rc = mosrx_launch_queue(&qp, tiles, kind, mosrx__tail_variant(c, dev_bytes, ntot), s->stream)))
 			return rc;
-		for (i = 0, pre = 0; h_match && i < nb; pre += b[i].n, i++)   /* the set per batch, same stream */
+		for (i = 0, pre = 0; h_match && i < nb; pre += b[i].n, i++) {   /* the set per batch, same stream */
+			msrc[i] = out_direct && b[i].n ? (uint32_t *)od[i].match : s->d_match + pre;
 			if ((rc = mosrx__bpf_launch_dev(c, s->h_qdesc[i].frames, b[i].frames_bytes, s->h_qdesc[i].off,
-			                                s->h_qdesc[i].len, b[i].n,
-			                                out_direct && b[i].n ? (uint32_t *)od[i].match : s->d_match + pre,
-			                                s->stream)))
+			                                s->h_qdesc[i].len, b[i].n, (uint32_t *)msrc[i], s->stream)))
 				return rc;
+		}
+		if (h_match)
+			go.match_src = msrc;
 	}
 	mosrx__stamp_next(NULL, NULL);   /* (a stamp pair no launch took is not left for the next one) */
 	if (c->timing && h_match && !fused)
@@ -1712,6 +1784,7 @@ int mosrx_time_host(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, mosrx_resul
  * it (records of 16 bytes, offsets, lengths; each rounded to 256 bytes). */
 #define STEER_TMP_QS ((MOSRX_STEER_QSLOTS * 4 + 255) & ~255)
 #define STEER_TMP_RND(x) (((size_t)(x) + 255) & ~(size_t)255)
+#define OP_IS_STEER(op) ((op) == MOSRX_OP_STEER || (op) == MOSRX_OP_STEER_GATHER || (op) == MOSRX_OP_STEER_GATHER_SIDE)
 static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
 {
 	uint32_t i, maxn = 0;
@@ -1720,8 +1793,10 @@ static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
 		maxn = b[i].n > maxn ? b[i].n : maxn;
 	c->steer_tmp_scratch = STEER_TMP_RND(mosrx_steer_scratch_bytes(maxn));
 	c->steer_tmp_n = maxn;
+	/* ... then MOSRX_OP_STEER_GATHER_SIDE's sources and outputs (flow hashes, masks, tcpinfo: 2 x 20 bytes a frame) */
 	stride = STEER_TMP_QS + c->steer_tmp_scratch + STEER_TMP_RND((size_t)maxn * 16) + STEER_TMP_RND((size_t)maxn * 4) +
-	         STEER_TMP_RND((size_t)maxn * 2);
+	         STEER_TMP_RND((size_t)maxn * 2) + 4 * STEER_TMP_RND((size_t)maxn * 4) +
+	         2 * STEER_TMP_RND((size_t)maxn * sizeof(mosrx_tcpinfo));
 	bytes = stride * (MOSRX_MAX_STREAMS + 1);
 	if (bytes > c->steer_tmp_bytes) {
 		HIPCHK(hipDeviceSynchronize());
@@ -1759,16 +1834,34 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 		return mosrx_steer_dev(c, out, b->n, arg, (uint32_t *)aux, (uint32_t *)blk, blk + STEER_TMP_QS,
 		                       c->steer_tmp_scratch, s);
 	}
-	case MOSRX_OP_STEER_GATHER: {
+	case MOSRX_OP_STEER_GATHER:
+	case MOSRX_OP_STEER_GATHER_SIDE: {
 		uint32_t k = 0;
 		uint8_t *blk, *qrec, *qoff, *qlen;
+		const int rb = op == MOSRX_OP_STEER_GATHER_SIDE ? arg & 0xFF : arg;
 		while (k < c->nxs && c->xs[k] != s)
 			k++;
 		blk = c->steer_tmp + (size_t)(k < c->nxs ? k + 1 : 0) * c->steer_tmp_stride;
 		qrec = blk + STEER_TMP_QS + c->steer_tmp_scratch;
 		qoff = qrec + STEER_TMP_RND((size_t)c->steer_tmp_n * 16);
 		qlen = qoff + STEER_TMP_RND((size_t)c->steer_tmp_n * 4);
-		return mosrx_steer_gather_dev(c, out, b->off, b->len, b->n, arg, (uint32_t *)aux, (uint32_t *)blk, qrec,
+		if (op == MOSRX_OP_STEER_GATHER_SIDE) {
+			/* which arrays: arg's MOSRX_SIDE_* bits (none: all three) */
+			const int which = (arg >> 8) ? arg >> 8 : MOSRX_SIDE_FHASH | MOSRX_SIDE_MATCH | MOSRX_SIDE_TCPINFO;
+			const size_t w = STEER_TMP_RND((size_t)c->steer_tmp_n * 4);
+			uint8_t *fh = qlen + STEER_TMP_RND((size_t)c->steer_tmp_n * 2), *ti = fh + 4 * w;
+			uint8_t *qti = ti + STEER_TMP_RND((size_t)c->steer_tmp_n * sizeof(mosrx_tcpinfo));
+			return mosrx_steer_gather_side_dev(c, out, b->off, b->len, b->n, rb, (uint32_t *)aux, (uint32_t *)blk, qrec,
+			                                   (uint32_t *)qoff, (uint16_t *)qlen,
+			                                   which & MOSRX_SIDE_FHASH ? (uint32_t *)fh : NULL,
+			                                   which & MOSRX_SIDE_FHASH ? (uint32_t *)(fh + w) : NULL,
+			                                   which & MOSRX_SIDE_MATCH ? (uint32_t *)(fh + 2 * w) : NULL,
+			                                   which & MOSRX_SIDE_MATCH ? (uint32_t *)(fh + 3 * w) : NULL,
+			                                   which & MOSRX_SIDE_TCPINFO ? (mosrx_tcpinfo *)ti : NULL,
+			                                   which & MOSRX_SIDE_TCPINFO ? (mosrx_tcpinfo *)qti : NULL,
+			                                   blk + STEER_TMP_QS, c->steer_tmp_scratch, s);
+		}
+		return mosrx_steer_gather_dev(c, out, b->off, b->len, b->n, rb, (uint32_t *)aux, (uint32_t *)blk, qrec,
 		                              (uint32_t *)qoff, (uint16_t *)qlen, blk + STEER_TMP_QS, c->steer_tmp_scratch, s);
 	}
 	default: return -EINVAL;
@@ -1857,13 +1950,14 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 {
 	int rc;
 	if (!c || !b || nb == 0 || iters == 0 || nstreams == 0 || nstreams > MOSRX_MAX_STREAMS ||
-	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER_GATHER || (op != MOSRX_OP_TX_CSUM && !out) ||
-	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI ||
-	      op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && !aux) ||
-	    ((op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && arg != 8 && arg != 16))
+	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER_GATHER_SIDE || (op != MOSRX_OP_TX_CSUM && !out) ||
+	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op)) &&
+	     !aux) ||
+	    ((op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && arg != 8 && arg != 16) ||
+	    (op == MOSRX_OP_STEER_GATHER_SIDE && (((arg & 0xFF) != 8 && (arg & 0xFF) != 16) || (arg >> 8) < 0 || (arg >> 8) > 7)))
 		return -EINVAL;
 	HIPCHK(hipSetDevice(c->device));
-	if ((op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && (rc = steer_tmp_reserve(c, b, nb)))
+	if (OP_IS_STEER(op) && (rc = steer_tmp_reserve(c, b, nb)))
 		return rc;
 	if (total_ms && (rc = time_streams(c, op, arg, b, nb, out, aux, iters, nstreams, total_ms)))
 		return rc;
@@ -1927,12 +2021,12 @@ int mosrx_time_op_dispatch(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, 
                            void *const *aux, uint32_t iters, float *avg_ms)
 {
 	struct op_run r = {op, arg, b, nb, out, aux};
-	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER_GATHER ||
+	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER_GATHER_SIDE ||
 	    (op != MOSRX_OP_TX_CSUM && !out) ||
-	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI ||
-	      op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && !aux))
+	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op)) &&
+	     !aux))
 		return -EINVAL;
-	if (op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER)   /* three launches: no single dispatch to stamp */
+	if (OP_IS_STEER(op))   /* three launches: no single dispatch to stamp */
 		return -ENOTSUP;
 	/* (the BPF ops are one launch with the fused kernel / the set's own kernel;
 	 * classify + the set's kernel, two, is refused by the launch count) */
@@ -2066,6 +2160,9 @@ struct mosrx_queue {
 	 * d_sdesc; gather: the scatter pass of a run is the gather form */
 	mosrx_gdesc *d_gdesc;
 	int gather;
+	/* ... and its side form (mosrx_queue_set_steer_gather_side), the third table */
+	mosrx_xdesc *d_xdesc;
+	int side;
 };
 
 int mosrx_queue_create_ex(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, void *const *d_out,
@@ -2201,19 +2298,27 @@ int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 		sp.gdesc = q->d_gdesc;
 		sp.gather = 1;
 	}
+	if (q->side) {
+		sp.xdesc = q->d_xdesc;
+		sp.side = 1;
+	}
 	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
 }
 
 static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
-                           void *const *d_qrec, uint32_t *const *d_qoff, uint16_t *const *d_qlen)
+                           void *const *d_qrec, uint32_t *const *d_qoff, uint16_t *const *d_qlen,
+                           uint32_t *const *d_qfhash, uint32_t *const *d_qmatch)
 {
 	mosrx_sdesc *h;
 	mosrx_gdesc *g = NULL;
+	mosrx_xdesc *x = NULL;
+	const int side = d_qfhash || d_qmatch;
 	uint32_t i, tiles = 0;
-	if (!c || !q || !d_idx != !d_qstart || (d_qrec && !d_idx) || !d_qoff != !d_qlen || (d_qoff && !d_qrec))
+	if (!c || !q || !d_idx != !d_qstart || (d_qrec && !d_idx) || !d_qoff != !d_qlen || (d_qoff && !d_qrec) ||
+	    (side && !d_qrec) || (d_qmatch && !q->match))
 		return -EINVAL;
 	if (!d_idx) {
-		q->steer = q->gather = 0;
+		q->steer = q->gather = q->side = 0;
 		return 0;
 	}
 	for (i = 0; i < q->nb; i++) {
@@ -2226,10 +2331,29 @@ static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx,
 			return -EINVAL;
 		if (d_qoff && (!d_qoff[i] || !d_qlen[i] || ((uintptr_t)d_qoff[i] & 3) || ((uintptr_t)d_qlen[i] & 1)))
 			return -EINVAL;
+		/* (a side array the queue's launches do not make has no source) */
+		if (d_qfhash && (!d_qfhash[i] || ((uintptr_t)d_qfhash[i] & 3) || !q->h_desc[i].fhash))
+			return -EINVAL;
+		if (d_qmatch && (!d_qmatch[i] || ((uintptr_t)d_qmatch[i] & 3) || !q->d_match[i]))
+			return -EINVAL;
 	}
-	if (!(h = calloc(q->nb, sizeof(*h))) || (d_qrec && !(g = calloc(q->nb, sizeof(*g))))) {
+	if (!(h = calloc(q->nb, sizeof(*h))) || (d_qrec && !(g = calloc(q->nb, sizeof(*g)))) ||
+	    (side && !(x = calloc(q->nb, sizeof(*x))))) {
 		free(h);
+		free(g);
 		return -ENOMEM;
+	}
+	for (i = 0; side && i < q->nb; i++) {
+		if (!q->h_desc[i].n)
+			continue;
+		if (d_qfhash) {
+			x[i].fhash = q->h_desc[i].fhash;
+			x[i].qfhash = d_qfhash[i];
+		}
+		if (d_qmatch) {
+			x[i].match = q->d_match[i];
+			x[i].qmatch = d_qmatch[i];
+		}
 	}
 	for (i = 0; d_qrec && i < q->nb; i++) {
 		if (!q->h_desc[i].n)
@@ -2248,42 +2372,55 @@ static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx,
 		h[i].tile_base = tiles;
 		tiles += (h[i].n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
 	}
-	q->steer = q->gather = 0;
+	q->steer = q->gather = q->side = 0;
 	if (hipSetDevice(c->device) != hipSuccess ||
 	    (!q->d_sdesc && hipMalloc((void **)&q->d_sdesc, (size_t)q->nb * sizeof(*h)) != hipSuccess) ||
 	    (g && !q->d_gdesc && hipMalloc((void **)&q->d_gdesc, (size_t)q->nb * sizeof(*g)) != hipSuccess) ||
+	    (x && !q->d_xdesc && hipMalloc((void **)&q->d_xdesc, (size_t)q->nb * sizeof(*x)) != hipSuccess) ||
 	    (!q->d_shist && hipMalloc((void **)&q->d_shist, ((size_t)tiles + 1) * MOSRX_STEER_BINS * 4) != hipSuccess)) {
 		free(h);
 		free(g);
+		free(x);
 		return -ENOMEM;
 	}
 	if (hipMemcpy(q->d_sdesc, h, (size_t)q->nb * sizeof(*h), hipMemcpyHostToDevice) != hipSuccess ||
-	    (g && hipMemcpy(q->d_gdesc, g, (size_t)q->nb * sizeof(*g), hipMemcpyHostToDevice) != hipSuccess)) {
+	    (g && hipMemcpy(q->d_gdesc, g, (size_t)q->nb * sizeof(*g), hipMemcpyHostToDevice) != hipSuccess) ||
+	    (x && hipMemcpy(q->d_xdesc, x, (size_t)q->nb * sizeof(*x), hipMemcpyHostToDevice) != hipSuccess)) {
 		free(h);
 		free(g);
+		free(x);
 		return -EIO;
 	}
 	free(h);
 	free(g);
+	free(x);
 	q->steer_tiles = tiles;
 	q->steer = 1;
 	q->gather = d_qrec != NULL;
+	q->side = side;
 	return 0;
 }
 
 int mosrx_queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart)
 {
-	return queue_set_steer(c, q, d_idx, d_qstart, NULL, NULL, NULL);
+	return queue_set_steer(c, q, d_idx, d_qstart, NULL, NULL, NULL, NULL, NULL);
 }
 
 int mosrx_queue_set_steer_gather(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
                                  void *const *d_qrec, uint32_t *const *d_qoff, uint16_t *const *d_qlen)
 {
-	if (!d_idx && !d_qstart && !d_qrec && !d_qoff && !d_qlen)   /* all NULL detaches */
-		return queue_set_steer(c, q, NULL, NULL, NULL, NULL, NULL);
+	return mosrx_queue_set_steer_gather_side(c, q, d_idx, d_qstart, d_qrec, d_qoff, d_qlen, NULL, NULL);
+}
+
+int mosrx_queue_set_steer_gather_side(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx,
+                                      uint32_t *const *d_qstart, void *const *d_qrec, uint32_t *const *d_qoff,
+                                      uint16_t *const *d_qlen, uint32_t *const *d_qfhash, uint32_t *const *d_qmatch)
+{
+	if (!d_idx && !d_qstart && !d_qrec && !d_qoff && !d_qlen && !d_qfhash && !d_qmatch)   /* all NULL detaches */
+		return queue_set_steer(c, q, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
 	if (!d_qrec)
 		return -EINVAL;
-	return queue_set_steer(c, q, d_idx, d_qstart, d_qrec, d_qoff, d_qlen);
+	return queue_set_steer(c, q, d_idx, d_qstart, d_qrec, d_qoff, d_qlen, d_qfhash, d_qmatch);
 }
 
 int mosrx_slot_steer(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart)
@@ -2297,13 +2434,23 @@ int mosrx_slot_steer(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *c
 	c->slot[slot].steer_qrec = NULL;
 	c->slot[slot].steer_qoff = NULL;
 	c->slot[slot].steer_qlen = NULL;
+	c->slot[slot].steer_qfhash = c->slot[slot].steer_qmatch = NULL;
+	c->slot[slot].steer_qtcpinfo = NULL;
 	return 0;
 }
 
 int mosrx_slot_steer_gather(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart,
                             void *const *h_qrec, uint32_t *const *h_qoff, uint16_t *const *h_qlen)
 {
-	const int none = !h_idx && !h_qstart && !h_qrec && !h_qoff && !h_qlen;
+	return mosrx_slot_steer_gather_side(c, slot, h_idx, h_qstart, h_qrec, h_qoff, h_qlen, NULL, NULL, NULL);
+}
+
+int mosrx_slot_steer_gather_side(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint32_t *const *h_qstart,
+                                 void *const *h_qrec, uint32_t *const *h_qoff, uint16_t *const *h_qlen,
+                                 uint32_t *const *h_qfhash, uint32_t *const *h_qmatch,
+                                 mosrx_tcpinfo *const *h_qtcpinfo)
+{
+	const int none = !h_idx && !h_qstart && !h_qrec && !h_qoff && !h_qlen && !h_qfhash && !h_qmatch && !h_qtcpinfo;
 	if (!c || slot < 0 || slot >= NSLOT || (!none && (!h_idx || !h_qstart || !h_qrec)) || !h_qoff != !h_qlen)
 		return -EINVAL;
 	if (c->slot[slot].busy)
@@ -2313,6 +2460,9 @@ int mosrx_slot_steer_gather(mosrx_ctx *c, int slot, uint32_t *const *h_idx, uint
 	c->slot[slot].steer_qrec = h_qrec;
 	c->slot[slot].steer_qoff = h_qoff;
 	c->slot[slot].steer_qlen = h_qlen;
+	c->slot[slot].steer_qfhash = h_qfhash;
+	c->slot[slot].steer_qmatch = h_qmatch;
+	c->slot[slot].steer_qtcpinfo = h_qtcpinfo;
 	return 0;
 }
 
@@ -2350,7 +2500,21 @@ int mosrx_steer_gather_dev(mosrx_ctx *c, const void *d_rec, const uint32_t *d_of
                            int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart, void *d_qrec, uint32_t *d_qoff,
                            uint16_t *d_qlen, void *d_scratch, size_t scratch_bytes, void *stream)
 {
+	return mosrx_steer_gather_side_dev(c, d_rec, d_off, d_len, n, rec_bytes, d_idx, d_qstart, d_qrec, d_qoff, d_qlen,
+	                                   NULL, NULL, NULL, NULL, NULL, NULL, d_scratch, scratch_bytes, stream);
+}
+
+int mosrx_steer_gather_side_dev(mosrx_ctx *c, const void *d_rec, const uint32_t *d_off, const uint16_t *d_len,
+                                uint32_t n, int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart, void *d_qrec,
+                                uint32_t *d_qoff, uint16_t *d_qlen, const uint32_t *d_fhash, uint32_t *d_qfhash,
+                                const uint32_t *d_match, uint32_t *d_qmatch, const mosrx_tcpinfo *d_tcpinfo,
+                                mosrx_tcpinfo *d_qtcpinfo, void *d_scratch, size_t scratch_bytes, void *stream)
+{
 	mosrx_sparams sp;
+	if (!d_fhash != !d_qfhash || !d_match != !d_qmatch || !d_tcpinfo != !d_qtcpinfo ||
+	    (((uintptr_t)d_fhash | (uintptr_t)d_qfhash | (uintptr_t)d_match | (uintptr_t)d_qmatch |
+	      (uintptr_t)d_tcpinfo | (uintptr_t)d_qtcpinfo) & 3))
+		return -EINVAL;
 	if (!c || !d_rec || !d_idx || !d_qstart || !d_qrec || !d_scratch || (rec_bytes != 8 && rec_bytes != 16) ||
 	    (((uintptr_t)d_idx | (uintptr_t)d_qstart | (uintptr_t)d_scratch) & 3) ||
 	    (((uintptr_t)d_rec | (uintptr_t)d_qrec) & (uintptr_t)(rec_bytes - 1)) ||
@@ -2371,6 +2535,8 @@ int mosrx_steer_gather_dev(mosrx_ctx *c, const void *d_rec, const uint32_t *d_of
 	sp.gone.qoff = d_qoff;
 	sp.gone.qlen = d_qlen;
 	sp.gather = 1;
+	sp.xone = (mosrx_xdesc){d_fhash, d_qfhash, d_match, d_qmatch, d_tcpinfo, d_qtcpinfo};
+	sp.side = d_qfhash || d_qmatch || d_qtcpinfo;   /* none: the plain gather form */
 	sp.hist = (uint32_t *)d_scratch;
 	sp.nb = 1;
 	sp.rec_bytes = (uint32_t)rec_bytes;
@@ -2390,6 +2556,8 @@ void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 		hipFree(q->d_sdesc);
 	if (q->d_gdesc)
 		hipFree(q->d_gdesc);
+	if (q->d_xdesc)
+		hipFree(q->d_xdesc);
 	if (q->d_shist)
 		hipFree(q->d_shist);
 	free(q->h_desc);

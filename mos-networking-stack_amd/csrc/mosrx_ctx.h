@@ -81,6 +81,14 @@ struct slot {
 	uint8_t *d_sqrec;
 	uint32_t *d_sqoff;
 	uint16_t *d_sqlen;
+	/* ... and of the gather's side form (mosrx_slot_steer_gather_side): the
+	 * armed outputs (each NULL: that array is not gathered), the side table
+	 * parallel to the other two, and the slot's own arrays for cap_n frames */
+	uint32_t *const *steer_qfhash, *const *steer_qmatch;
+	mosrx_tcpinfo *const *steer_qtcpinfo;
+	mosrx_xdesc *h_xdesc, *d_xdesc;
+	uint32_t *d_sqfh, *d_sqmt;
+	mosrx_tcpinfo *d_sqti;
 	int timed;
 	int busy;
 };

@@ -42,6 +42,21 @@ typedef struct mosrx_gdesc {
 	uint16_t       *qlen;     /* n, or NULL with qoff */
 } mosrx_gdesc;
 
+/* The side arrays of one batch, parallel to its mosrx_sdesc and mosrx_gdesc:
+ * the gather form's side form also stores, in the order of idx,
+ *   qfhash[j] = fhash[idx[j]], qmatch[j] = match[idx[j]]   u32
+ *   qtcpinfo[j] = tcpinfo[idx[j]]                            12 bytes, whole
+ * each pair on its own: a NULL destination is not gathered (nothing read,
+ * nothing written).  All pointers 4-byte aligned.  48 bytes. */
+typedef struct mosrx_xdesc {
+	const uint32_t      *fhash;
+	uint32_t            *qfhash;    /* n, or NULL */
+	const uint32_t      *match;
+	uint32_t            *qmatch;    /* n, or NULL */
+	const mosrx_tcpinfo *tcpinfo;
+	mosrx_tcpinfo       *qtcpinfo;  /* n, or NULL */
+} mosrx_xdesc;
+
 typedef struct mosrx_sparams {
 	const mosrx_sdesc *desc;  /* nb entries in device-visible memory, or NULL: the one batch in `one` */
 	mosrx_sdesc        one;
@@ -52,12 +67,16 @@ typedef struct mosrx_sparams {
 	uint32_t           gather;      /* 1: the scatter pass is the gather form, over gdesc[] (with desc) or gone */
 	const mosrx_gdesc *gdesc; /* nb entries parallel to desc[], or NULL */
 	mosrx_gdesc        gone;  /* the gather of `one` */
+	const mosrx_xdesc *xdesc; /* nb entries parallel to desc[] / gdesc[], or NULL */
+	mosrx_xdesc        xone;  /* the side arrays of `one` */
+	uint32_t           side;  /* 1 (with gather): the gather pass is its side form, over xdesc[] or xone */
 } mosrx_sparams;
 
 /* The three launches (histogram, scan, scatter) on `stream` (a hipStream_t);
  * 0, -EINVAL or -EIO.  Allocates nothing.  gather == 0 is the plain scatter
  * whatever gdesc / gone hold; with gather the single-batch form's pointers are
- * checked here (-EINVAL), a table's by whoever filled it. */
+ * checked here (-EINVAL), a table's by whoever filled it.  side without gather
+ * is -EINVAL; side == 0 is the gather form whatever xdesc / xone hold. */
 int mosrx_launch_steer(const mosrx_sparams *sp, void *stream);
 
 #ifdef __cplusplus

@@ -248,8 +248,16 @@ __device__ __forceinline__ uint32_t steer_batch_index(const mosrx_sparams &sp, u
 	return lo;
 }
 
-template <uint32_t RB>
-__global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_gather_kernel(mosrx_sparams sp)
+// Its side form (SIDE, mosrx_xdesc) also stores the frame's flow hash, match
+// mask and tcpinfo at pos, each array on its own (present or not is uniform
+// over the workgroup).  Their loads go out with the record's, before the first
+// barrier: they need the frame's index, not its position.  The 12-byte tcpinfo
+// moves as three dwords.  SIDE is a template parameter of the body: the plain
+// gather kernels are the code they were.
+static_assert(sizeof(mosrx_tcpinfo) == 12 && sizeof(mosrx_xdesc) == 48, "side arrays: 12-byte tcpinfo, 48-byte descriptor");
+
+template <uint32_t RB, bool SIDE>
+__device__ __forceinline__ void steer_gather_body(const mosrx_sparams &sp)
 {
 	typedef decltype(steer_rec<RB>::v) vec_t;
 	__shared__ uint32_t s_row[STEER_ROWS][MOSRX_STEER_BINS];
@@ -261,30 +269,55 @@ __global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_gather_kernel
 	__syncthreads();
 	mosrx_sdesc d;
 	mosrx_gdesc g;
+	mosrx_xdesc x = {};
 	if (sp.desc) {
 		const uint32_t k = steer_batch_index(sp, blockIdx.x);
 		d = sp.desc[k];
 		g = sp.gdesc[k];
+		if constexpr (SIDE)
+			x = sp.xdesc[k];
 	} else {
 		d = sp.one;
 		g = sp.gone;
+		if constexpr (SIDE)
+			x = sp.xone;
 	}
 	const bool descs = g.qoff != nullptr;   // uniform over the workgroup
+	const bool has_fh = SIDE && x.qfhash != nullptr, has_mt = SIDE && x.qmatch != nullptr;
+	const bool has_ti = SIDE && x.qtcpinfo != nullptr;
 	const uint32_t row0 = wave * STEER_SLICES;
 	const uint32_t first = (blockIdx.x - d.tile_base) * MOSRX_STEER_TILE + row0 * 64u;
 	steer_rec<RB> r[STEER_SLICES];
 	uint32_t key[STEER_SLICES], rank[STEER_SLICES], foff[STEER_SLICES], flen[STEER_SLICES];
+	uint32_t ffh[SIDE ? STEER_SLICES : 1u], fmt[SIDE ? STEER_SLICES : 1u];
+	uint32_t ti0[SIDE ? STEER_SLICES : 1u], ti1[SIDE ? STEER_SLICES : 1u], ti2[SIDE ? STEER_SLICES : 1u];
 #pragma unroll
 	for (uint32_t s = 0; s < STEER_SLICES; s++) {
 		const uint32_t i = first + s * 64u + lane;
 		const bool valid = i < d.n;
 		r[s].v = vec_t{};
 		foff[s] = flen[s] = 0;
+		if constexpr (SIDE) {
+			ffh[s] = fmt[s] = 0;
+			ti0[s] = ti1[s] = ti2[s] = 0;
+		}
 		if (valid) {
 			r[s].v = *reinterpret_cast<const vec_t *>(d.rec + (uint64_t)i * RB);
 			if (descs) {
 				foff[s] = g.off[i];
 				flen[s] = g.len[i];
+			}
+			if constexpr (SIDE) {
+				if (has_fh)
+					ffh[s] = x.fhash[i];
+				if (has_mt)
+					fmt[s] = x.match[i];
+				if (has_ti) {
+					const uint32_t *w = reinterpret_cast<const uint32_t *>(x.tcpinfo) + (uint64_t)i * 3u;
+					ti0[s] = w[0];
+					ti1[s] = w[1];
+					ti2[s] = w[2];
+				}
 			}
 		}
 		key[s] = valid ? r[s].key() : 0u;
@@ -316,9 +349,33 @@ __global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_gather_kernel
 					g.qoff[pos] = foff[s];
 					g.qlen[pos] = (uint16_t)flen[s];
 				}
+				if constexpr (SIDE) {
+					if (has_fh)
+						x.qfhash[pos] = ffh[s];
+					if (has_mt)
+						x.qmatch[pos] = fmt[s];
+					if (has_ti) {
+						uint32_t *w = reinterpret_cast<uint32_t *>(x.qtcpinfo) + (uint64_t)pos * 3u;
+						w[0] = ti0[s];
+						w[1] = ti1[s];
+						w[2] = ti2[s];
+					}
+				}
 			}
 		}
 	}
+}
+
+template <uint32_t RB>
+__global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_gather_kernel(mosrx_sparams sp)
+{
+	steer_gather_body<RB, false>(sp);
+}
+
+template <uint32_t RB>
+__global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_gather_side_kernel(mosrx_sparams sp)
+{
+	steer_gather_body<RB, true>(sp);
 }
 
 static int gather_ok(const mosrx_sparams *sp)
@@ -337,12 +394,30 @@ static int gather_ok(const mosrx_sparams *sp)
 	return 1;
 }
 
+// The single-batch form's side pairs: both pointers or neither, 4-byte aligned.
+static int side_ok(const mosrx_sparams *sp)
+{
+	const mosrx_xdesc *x = &sp->xone;
+	if (!sp->gather)
+		return 0;
+	if (sp->desc)
+		return sp->xdesc != NULL;
+	if (!sp->one.n)
+		return 1;
+	if (!x->fhash != !x->qfhash || !x->match != !x->qmatch || !x->tcpinfo != !x->qtcpinfo)
+		return 0;
+	return !(((uintptr_t)x->fhash | (uintptr_t)x->qfhash | (uintptr_t)x->match | (uintptr_t)x->qmatch |
+	          (uintptr_t)x->tcpinfo | (uintptr_t)x->qtcpinfo) & 3);
+}
+
 extern "C" int mosrx_launch_steer(const mosrx_sparams *sp, void *stream)
 {
 	const hipStream_t s = (hipStream_t)stream;
 	if (!sp || !sp->hist || (sp->rec_bytes != 8u && sp->rec_bytes != 16u) || (sp->desc && sp->nb == 0))
 		return -EINVAL;
 	if (sp->gather && !gather_ok(sp))
+		return -EINVAL;
+	if (sp->side && !side_ok(sp))
 		return -EINVAL;
 	if (sp->total_tiles == 0 && !sp->desc)
 		return 0;
@@ -351,6 +426,10 @@ extern "C" int mosrx_launch_steer(const mosrx_sparams *sp, void *stream)
 	hipLaunchKernelGGL(mosrx_steer_scan_kernel, dim3(sp->desc ? sp->nb : 1u), dim3(SCAN_THREADS), 0, s, *sp);
 	if (sp->total_tiles && !sp->gather)
 		hipLaunchKernelGGL(mosrx_steer_scatter_kernel, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
+	else if (sp->total_tiles && sp->side && sp->rec_bytes == 8u)
+		hipLaunchKernelGGL(mosrx_steer_gather_side_kernel<8u>, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
+	else if (sp->total_tiles && sp->side)
+		hipLaunchKernelGGL(mosrx_steer_gather_side_kernel<16u>, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
 	else if (sp->total_tiles && sp->rec_bytes == 8u)
 		hipLaunchKernelGGL(mosrx_steer_gather_kernel<8u>, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
 	else if (sp->total_tiles)

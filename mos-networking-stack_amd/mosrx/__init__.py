@@ -106,6 +106,8 @@ TX_IP_CSUM, TX_TCP_CSUM = 1 << 4, 1 << 5   # MOS_UPDATE_IP_CHKSUM / MOS_UPDATE_T
 OP_CLASSIFY, OP_CLASSIFY_FH, OP_BPF, OP_TX_CSUM, OP_CLASSIFY_BPF, OP_CLASSIFY_TI, OP_TX_CHECKS = 0, 1, 2, 3, 4, 5, 6
 OP_STEER = 7           # MOSRX_OP_STEER: the steer sequence over a batch's records (arg = rec_bytes)
 OP_STEER_GATHER = 8    # MOSRX_OP_STEER_GATHER: ... with the scatter launch in its gather form
+OP_STEER_GATHER_SIDE = 9   # MOSRX_OP_STEER_GATHER_SIDE: ... in its side form (arg = rec_bytes | SIDE_* bits << 8)
+SIDE_FHASH, SIDE_MATCH, SIDE_TCPINFO = 1, 2, 4   # MOSRX_SIDE_*
 STEER_QSLOTS = 257     # MOSRX_STEER_QSLOTS: qstart entries per batch
 # include/mosrx.h mosrx_tx_check: the TX checks of a frame, the frame untouched
 TX_CHECK_DTYPE = np.dtype([("ip_check", "<u2"), ("tcp_check", "<u2"), ("what", "u1"), ("ihl", "u1"),
@@ -149,6 +151,12 @@ class QueueView(C.Structure):
     """mosrx_queue_view (dev_ioctl(MOSRX_PKT_RX_QUEUE))."""
     _fields_ = [("q", C.c_uint32), ("n", C.c_uint32), ("rec", C.c_void_p), ("rec_bytes", C.c_uint32),
                 ("off", C.c_void_p), ("len", C.c_void_p), ("idx", C.c_void_p), ("frames", C.c_void_p)]
+
+
+class QueueSide(C.Structure):
+    """mosrx_queue_side (dev_ioctl(MOSRX_PKT_RX_QUEUE_SIDE))."""
+    _fields_ = [("q", C.c_uint32), ("n", C.c_uint32), ("fhash", C.c_void_p), ("match", C.c_void_p),
+                ("tcpinfo", C.c_void_p)]
 
 
 class HubStats(C.Structure):
@@ -369,6 +377,10 @@ def lib():
                                                  C.POINTER(P)]),
             "mosrx_slot_steer_gather": (I, [P, I, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P),
                                             C.POINTER(P)]),
+            "mosrx_steer_gather_side_dev": (I, [P, P, P, P, U32, I, P, P, P, P, P, P, P, P, P, P, P, P, C.c_size_t,
+                                                P]),
+            "mosrx_queue_set_steer_gather_side": (I, [P, P] + [C.POINTER(P)] * 7),
+            "mosrx_slot_steer_gather_side": (I, [P, I] + [C.POINTER(P)] * 8),
             "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
             "mosrx_hub_endpoint": (P, [P, U32]),
             "mosrx_hub_stats_get": (I, [P, P]),
@@ -887,6 +899,34 @@ class Context:
         if sync:
             _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
 
+    def steer_gather_side_dev(self, d_rec: int, d_off: int | None, d_len: int | None, n: int, rec_bytes: int,
+                              d_idx: int, d_qstart: int, d_qrec: int, d_qoff: int | None, d_qlen: int | None,
+                              d_scratch: int, scratch_bytes: int, fhash: tuple | None = None,
+                              match: tuple | None = None, tcpinfo: tuple | None = None, sync: bool = True,
+                              stream: int | None = None) -> None:
+        """mosrx_steer_gather_side_dev: steer_gather_dev, with each side array given
+        as a (source, destination) pair of device pointers also stored in the order of idx."""
+        pairs = [p if p is not None else (None, None) for p in (fhash, match, tcpinfo)]
+        _chk(lib().mosrx_steer_gather_side_dev(self.handle, d_rec, d_off, d_len, n, rec_bytes, d_idx, d_qstart, d_qrec,
+                                               d_qoff, d_qlen, *pairs[0], *pairs[1], *pairs[2], d_scratch,
+                                               scratch_bytes, stream), "mosrx_steer_gather_side_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
+    def slot_steer_gather_side(self, slot: int, idx: list | None, qstart: list | None = None,
+                               qrec: list | None = None, qoff: list | None = None, qlen: list | None = None,
+                               qfhash: list | None = None, qmatch: list | None = None,
+                               qtcpinfo: list | None = None) -> None:
+        """mosrx_slot_steer_gather_side: slot_steer_gather with per-batch host
+        destinations for the flow hashes, match masks and pkt_info (any may be None)."""
+        if idx is None:
+            self._steer_arm = None
+            _chk(lib().mosrx_slot_steer_gather_side(self.handle, slot, *([None] * 8)), "mosrx_slot_steer_gather_side")
+            return
+        self._steer_arm = tuple((C.c_void_p * len(a))(*a) if a is not None else None
+                                for a in (idx, qstart, qrec, qoff, qlen, qfhash, qmatch, qtcpinfo))
+        _chk(lib().mosrx_slot_steer_gather_side(self.handle, slot, *self._steer_arm), "mosrx_slot_steer_gather_side")
+
     def slot_steer_gather(self, slot: int, idx: list | None, qstart: list | None = None, qrec: list | None = None,
                           qoff: list | None = None, qlen: list | None = None) -> None:
         """mosrx_slot_steer_gather: slot_steer with per-batch gather outputs (host
@@ -944,16 +984,16 @@ class Context:
                 d.d_tinfo = DevBuffer(self, max(d.n * 12, 12))
             if op in (OP_BPF, OP_CLASSIFY_BPF) and d.d_match is None:
                 d.d_match = DevBuffer(self, max(d.n * 4, 4))
-            if op in (OP_STEER, OP_STEER_GATHER) and d.d_sidx is None:
+            if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) and d.d_sidx is None:
                 d.d_sidx = DevBuffer(self, max(d.n * 4, 4))
         bs = (Batch * len(dbs))(*[d.batch() for d in dbs])
         # OP_STEER reads the records a classify call left: the compact ones for arg == 8
         outs = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_BPF else
-                                          d.d_out8.ptr if op in (OP_STEER, OP_STEER_GATHER) and arg == 8
+                                          d.d_out8.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) and (arg & 0xFF) == 8
                                           else d.d_out.ptr) for d in dbs])
         aux = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_CLASSIFY_BPF else
                                          d.d_tinfo.ptr if op == OP_CLASSIFY_TI else
-                                         d.d_sidx.ptr if op in (OP_STEER, OP_STEER_GATHER) else
+                                         d.d_sidx.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) else
                                          (d.d_fhash.ptr if d.d_fhash else None)) for d in dbs])
         tot, avg = C.c_float(), C.c_float()
         _chk(lib().mosrx_time_op(self.handle, op, arg, bs, len(dbs), outs, aux, iters, nstreams,
@@ -1076,6 +1116,16 @@ class Queue:
         arrs = [(C.c_void_p * len(a))(*a) if a is not None else None for a in (idx, qstart, qrec, qoff, qlen)]
         _chk(lib().mosrx_queue_set_steer_gather(self.ctx.handle, self.handle, *arrs), "mosrx_queue_set_steer_gather")
 
+    def set_steer_gather_side(self, idx: list | None, qstart: list | None = None, qrec: list | None = None,
+                              qoff: list | None = None, qlen: list | None = None, qfhash: list | None = None,
+                              qmatch: list | None = None) -> None:
+        """mosrx_queue_set_steer_gather_side: set_steer_gather with per-batch device
+        destinations for the queue's own flow hashes / match masks; idx None detaches."""
+        arrs = [(C.c_void_p * len(a))(*a) if a is not None else None
+                for a in (idx, qstart, qrec, qoff, qlen, qfhash, qmatch)]
+        _chk(lib().mosrx_queue_set_steer_gather_side(self.ctx.handle, self.handle, *arrs),
+             "mosrx_queue_set_steer_gather_side")
+
     def run(self, sync: bool = True):
         _chk(lib().mosrx_queue_run(self.ctx.handle, self.handle, None), "mosrx_queue_run")
         if sync:
@@ -1142,6 +1192,7 @@ PKT_RX_STATE, PKT_RX_RECLASSIFY, PKT_SET_BPF, PKT_RX_FHASH = 0x14, 0x15, 0x16, 0
 PKT_RX_RESULTS8 = 0x18
 PKT_RX_STEER = 0x19
 PKT_RX_QUEUE = 0x1A
+PKT_RX_QUEUE_SIDE = 0x1B
 QUEUE_PROBE = 0xFFFFFFFF
 
 
@@ -1189,7 +1240,8 @@ class GpuBackend:
         if direct_frames is not None:
             cfg.direct_frames = direct_frames   # ... and up to this many frames
         cfg.steer = int(steer)              # 1: every group steered on the GPU (steer_view, run_loop_queues);
-        #                                     2: and gathered queue-major (queue_view, Hub)
+        #                                     2: and gathered queue-major (queue_view, Hub);
+        #                                     3: and the side arrays with them (queue_side)
         if params is not None:
             cfg.params = params
         self.params = Params.from_buffer_copy(cfg.params)
@@ -1276,6 +1328,16 @@ class GpuBackend:
         if self._ioctl(self.ctx, ifidx, PKT_RX_QUEUE, C.byref(v)):
             return None
         return _queue_view_arrays(v)
+
+    def queue_side(self, ifidx: int, q: int):
+        """dev_ioctl(MOSRX_PKT_RX_QUEUE_SIDE): queue q's share of the exposed batch's
+        side arrays as (fhash[n], match[n], tcpinfo[n]), each None where the batch
+        has none; None unless the batch was gathered with cfg.steer = 3."""
+        v = QueueSide()
+        v.q = q
+        if self._ioctl(self.ctx, ifidx, PKT_RX_QUEUE_SIDE, C.byref(v)):
+            return None
+        return _queue_side_arrays(v)
 
     def run_loop_queues(self, nq: int, fn=None, args: list | None = None, max_rounds: int = 0) -> RxStats:
         """mosrx_rx_loop_queues over this backend: fn (a _PKTFN callback) gets
@@ -1370,6 +1432,18 @@ def _queue_view_arrays(v: QueueView):
     ln = np.ctypeslib.as_array(C.cast(v.len, C.POINTER(C.c_uint16)), (n,)).copy()
     idx = np.ctypeslib.as_array(C.cast(v.idx, C.POINTER(C.c_uint32)), (n,)).copy()
     return rec, off, ln, idx, v.frames
+
+
+def _queue_side_arrays(v: QueueSide):
+    n = int(v.n)
+
+    def arr(p, dtype):
+        if not p:
+            return None
+        if n == 0:
+            return np.zeros(0, dtype)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), (n * dtype.itemsize,)).view(dtype).copy()
+    return arr(v.fhash, np.dtype(np.uint32)), arr(v.match, np.dtype(np.uint32)), arr(v.tcpinfo, TCPINFO_DTYPE)
 
 
 def hub_module(module_lib=None) -> IoModuleFunc:
