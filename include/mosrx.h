@@ -355,6 +355,25 @@ int  mosrx_slot_steer_gather_side(mosrx_ctx *c, int slot, uint32_t *const *h_idx
 #define MOSRX_SIDE_MATCH   2
 #define MOSRX_SIDE_TCPINFO 4
 
+/* ---- the one-launch steer form: small batches, direct groups ----------------- */
+/* Histogram, scan and scatter (or its gather / side form) in one kernel, one
+ * workgroup per batch, for batches whose steering is bound by launch latency
+ * rather than by the walk: the same outputs as the three launches, bit for
+ * bit.  Per context and off by default: with a limit of max_frames > 0 every
+ * steer entry point (mosrx_steer_dev and its gather / side forms, a steered
+ * mosrx_queue_run, an armed group submit, the MOSRX_OP_STEER* timing ops)
+ * issues the one launch when every batch of that launch has n <= max_frames,
+ * and the three launches otherwise (one larger batch sends the whole launch
+ * there).  0: the three launches, always.  MOSRX_STEER_ONE_MAX bounds one
+ * workgroup's walk (32 tiles); a limit above it is -EINVAL and changes
+ * nothing.  The limit worth setting is far smaller: DESIGN.md §4.12.  The
+ * device calls still take (and in this form leave untouched) their scratch. */
+#define MOSRX_STEER_ONE_MAX 65536u
+int      mosrx_set_steer_one(mosrx_ctx *c, uint32_t max_frames);
+uint32_t mosrx_get_steer_one(const mosrx_ctx *c);
+/* Steer launches of this context that took the one-launch form so far. */
+uint64_t mosrx_steer_one_count(const mosrx_ctx *c);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned

@@ -306,6 +306,15 @@ int  mosrx_gpu_module_configure(const mosrx_gpu_module_cfg *cfg);
 /* The configuration in effect (after load_module_upper_half took mOS's own
  * state into it, when built inside mOS). */
 int  mosrx_gpu_module_get_cfg(mosrx_gpu_module_cfg *cfg);
+/* With cfg.steer: a group whose batches all have at most max_frames frames is
+ * steered by one launch instead of three (mosrx_set_steer_one on every context
+ * opened afterwards: the same outputs, so views, ioctls and the hub do not
+ * change; what to set).  Before init_handle, like
+ * mosrx_gpu_module_configure.  0 (the default): never.  Negative or above
+ * MOSRX_STEER_ONE_MAX: -EINVAL, and the setting stays.  A setting of the
+ * module, not a field of mosrx_gpu_module_cfg: the struct's layout stands. */
+int     mosrx_gpu_module_set_steer_one(int32_t max_frames);
+int32_t mosrx_gpu_module_get_steer_one(void);
 /* Bind a thread context pointer to a cpu index before init_handle.  Unbound
  * contexts get their cpu from ctx->cpu inside an mOS build (the mTCP core,
  * mtcp.h:306, set by MTCPRunThread before init_handle, core.c:1302-1313) and
@@ -358,6 +367,9 @@ typedef struct mosrx_gpu_module_stats {
 /* Time every kernel this thread's contexts launch (for the stats above). */
 int  mosrx_gpu_module_set_timing(struct mtcp_thread_context *ctx, int on);
 int  mosrx_gpu_module_stats_of(struct mtcp_thread_context *ctx, mosrx_gpu_module_stats *st);
+/* Steered groups of this thread's contexts that took the one-launch form
+ * (mosrx_gpu_module_set_steer_one; mosrx_steer_one_count summed over the netdevs). */
+uint64_t mosrx_gpu_module_steer_one_count(struct mtcp_thread_context *ctx);
 
 /* ---- RunMainLoop-shaped driver (core.c:897-909) ---- */
 typedef struct mosrx_rx_stats {

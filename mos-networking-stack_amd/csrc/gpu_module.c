@@ -161,6 +161,7 @@ static pthread_mutex_t g_lock = PTHREAD_MUTEX_INITIALIZER;
 static struct { struct mtcp_thread_context *ctx; int cpu; struct gpu_priv *priv; } g_tab[MAX_THREADS];
 static mosrx_source *g_src_cpu[MAX_THREADS][MOSRX_MAX_DEVICES];
 static int g_next_cpu;
+static int32_t g_steer_one;   /* mosrx_gpu_module_set_steer_one: frames; 0: every steered group takes three launches */
 
 void mosrx_gpu_module_cfg_default(mosrx_gpu_module_cfg *cfg)
 {
@@ -194,6 +195,18 @@ int mosrx_gpu_module_configure(const mosrx_gpu_module_cfg *cfg)
 	pthread_mutex_unlock(&g_lock);
 	return 0;
 }
+
+int mosrx_gpu_module_set_steer_one(int32_t max_frames)
+{
+	if (max_frames < 0 || (uint32_t)max_frames > MOSRX_STEER_ONE_MAX)
+		return -EINVAL;
+	pthread_mutex_lock(&g_lock);
+	g_steer_one = max_frames;
+	pthread_mutex_unlock(&g_lock);
+	return 0;
+}
+
+int32_t mosrx_gpu_module_get_steer_one(void) { return g_steer_one; }
 
 int mosrx_gpu_module_get_cfg(mosrx_gpu_module_cfg *cfg)
 {
@@ -298,6 +311,17 @@ int mosrx_gpu_module_set_timing(struct mtcp_thread_context *ctx, int on)
 		if (pv->ifs[i].mc)
 			mosrx_set_timing(pv->ifs[i].mc, on);
 	return 0;
+}
+
+uint64_t mosrx_gpu_module_steer_one_count(struct mtcp_thread_context *ctx)
+{
+	struct gpu_priv *pv = priv_of(ctx);
+	uint64_t sum = 0;
+	uint32_t i;
+	for (i = 0; pv && g_steer_one > 0 && i < g_cfg.num_ifs; i++)
+		if (pv->ifs[i].mc)
+			sum += mosrx_steer_one_count(pv->ifs[i].mc);
+	return sum;
 }
 
 int mosrx_gpu_module_stats_of(struct mtcp_thread_context *ctx, mosrx_gpu_module_stats *st)
@@ -593,6 +617,12 @@ static void gpu_init_handle(struct mtcp_thread_context *ctx)
 		/* small groups (light load) with no copies: the kernel reads the pinned
 		 * staging and writes the pinned records in place */
 		mosrx_set_direct(is->mc, (uint64_t)g_cfg.direct_kb << 10, g_cfg.direct_frames);
+		/* mosrx_gpu_module_set_steer_one: a steered group whose batches all fit is steered
+		 * by one launch (left at 0 the context is not touched: off is its default) */
+		if (g_steer_one && (rc = mosrx_set_steer_one(is->mc, (uint32_t)g_steer_one))) {
+			fprintf(stderr, "[mosrx] gpu_module: steer_one %d: %s\n", g_steer_one, mosrx_strerror(rc));
+			exit(EXIT_FAILURE);
+		}
 		is->src = (cpu < MAX_THREADS && g_src_cpu[cpu][i]) ? g_src_cpu[cpu][i] : g_cfg.src[i];
 		is->cur = is->inflight = -1;
 		if (g_cfg.bpf_nprog && (rc = mosrx_bpf_set(is->mc, g_cfg.bpf_progs, g_cfg.bpf_nprog))) {

@@ -1114,6 +1114,19 @@ static int gather_outputs(int device, const mosrx_batch *b, uint32_t nb, size_t 
 	return 1;
 }
 
+/* A steer launch of this context whose largest batch has maxn frames: the one
+ * launch when the context's limit admits every batch (mosrx_set_steer_one),
+ * else -- and always with the limit at 0 -- the three launches. */
+static int steer_launch(mosrx_ctx *c, mosrx_sparams *sp, uint32_t maxn, void *stream)
+{
+	int rc;
+	sp->fused = c->steer_one && maxn <= c->steer_one;
+	rc = mosrx_launch_steer(sp, stream);
+	if (!rc && sp->fused)
+		c->steer_one_count++;
+	return rc;
+}
+
 /* The steer launches of an armed group, behind its classify launch on the
  * slot's stream: over the records where that launch wrote them (s->h_qdesc),
  * into the caller's pinned arrays (in_place: steer_outputs filled the table)
@@ -1122,11 +1135,11 @@ static int gather_outputs(int device, const mosrx_batch *b, uint32_t nb, size_t 
  * (g->qrec) the scatter pass is its gather form, over the descriptors where
  * the classify launch read them; with side outputs its side form, over the
  * side arrays where the group's launches wrote them. */
-static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
+static int group_steer(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
                        uint32_t *const *h_idx, uint32_t *const *h_qstart, const struct gather_out *g)
 {
 	mosrx_sparams sp;
-	uint32_t i, tiles = 0;
+	uint32_t i, tiles = 0, maxn = 0;
 	uint64_t pre = 0;
 	int rc;
 	memset(&sp, 0, sizeof(sp));
@@ -1140,6 +1153,8 @@ static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t
 		d->n = b[i].n;
 		d->tile_base = tiles;
 		tiles += (b[i].n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
+		if (b[i].n > maxn)
+			maxn = b[i].n;
 		if (g->qrec) {
 			mosrx_gdesc *gd = &s->h_gdesc[i];
 			if (!in_place) {
@@ -1178,7 +1193,7 @@ static int group_steer(struct slot *s, const mosrx_batch *b, uint32_t nb, size_t
 	sp.nb = nb;
 	sp.rec_bytes = (uint32_t)rsz;
 	sp.total_tiles = tiles;
-	if ((rc = mosrx_launch_steer(&sp, s->stream)))
+	if ((rc = steer_launch(c, &sp, maxn, s->stream)))
 		return rc;
 	for (i = 0, pre = 0; g->qrec && !in_place && i < nb; pre += b[i].n, i++) {
 		if (!b[i].n)
@@ -1386,7 +1401,7 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	if (c->timing && h_match && !fused)
 		HIPCHK(hipEventRecord(s->kev1, s->stream));
 	s->timed = c->timing;
-	if (h_sidx && (rc = group_steer(s, b, nb, rsz, out_direct, h_sidx, h_sqs, &go)))
+	if (h_sidx && (rc = group_steer(c, s, b, nb, rsz, out_direct, h_sidx, h_sqs, &go)))
 		return rc;
 	/* results: one copy when the host buffers follow each other, else per batch */
 	for (i = 0, pre = 0; !out_direct && i < nb;) {
@@ -2155,6 +2170,7 @@ struct mosrx_queue {
 	mosrx_sdesc *d_sdesc;
 	uint32_t *d_shist;
 	uint32_t steer_tiles;
+	uint32_t steer_maxn;   /* the largest batch, kept at attach: a run takes the one-launch form by it */
 	int steer;
 	/* its gather form (mosrx_queue_set_steer_gather): the table parallel to
 	 * d_sdesc; gather: the scatter pass of a run is the gather form */
@@ -2302,7 +2318,7 @@ int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 		sp.xdesc = q->d_xdesc;
 		sp.side = 1;
 	}
-	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
+	return steer_launch(c, &sp, q->steer_maxn, stream ? stream : (void *)c->stream);
 }
 
 static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
@@ -2313,7 +2329,7 @@ static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx,
 	mosrx_gdesc *g = NULL;
 	mosrx_xdesc *x = NULL;
 	const int side = d_qfhash || d_qmatch;
-	uint32_t i, tiles = 0;
+	uint32_t i, tiles = 0, maxn = 0;
 	if (!c || !q || !d_idx != !d_qstart || (d_qrec && !d_idx) || !d_qoff != !d_qlen || (d_qoff && !d_qrec) ||
 	    (side && !d_qrec) || (d_qmatch && !q->match))
 		return -EINVAL;
@@ -2371,6 +2387,8 @@ static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx,
 		h[i].qstart = h[i].n ? d_qstart[i] : NULL;
 		h[i].tile_base = tiles;
 		tiles += (h[i].n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
+		if (h[i].n > maxn)
+			maxn = h[i].n;
 	}
 	q->steer = q->gather = q->side = 0;
 	if (hipSetDevice(c->device) != hipSuccess ||
@@ -2395,6 +2413,7 @@ static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx,
 	free(g);
 	free(x);
 	q->steer_tiles = tiles;
+	q->steer_maxn = maxn;
 	q->steer = 1;
 	q->gather = d_qrec != NULL;
 	q->side = side;
@@ -2474,6 +2493,18 @@ size_t mosrx_steer_scratch_bytes(uint32_t n)
 
 uint32_t mosrx_steer_tile(void) { return MOSRX_STEER_TILE; }
 
+int mosrx_set_steer_one(mosrx_ctx *c, uint32_t max_frames)
+{
+	if (!c || max_frames > MOSRX_STEER_ONE_MAX)
+		return -EINVAL;
+	c->steer_one = max_frames;
+	return 0;
+}
+
+uint32_t mosrx_get_steer_one(const mosrx_ctx *c) { return c ? c->steer_one : 0; }
+
+uint64_t mosrx_steer_one_count(const mosrx_ctx *c) { return c ? c->steer_one_count : 0; }
+
 int mosrx_steer_dev(mosrx_ctx *c, const void *d_rec, uint32_t n, int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart,
                     void *d_scratch, size_t scratch_bytes, void *stream)
 {
@@ -2493,7 +2524,7 @@ int mosrx_steer_dev(mosrx_ctx *c, const void *d_rec, uint32_t n, int rec_bytes, 
 	sp.nb = 1;
 	sp.rec_bytes = (uint32_t)rec_bytes;
 	sp.total_tiles = (n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
-	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
+	return steer_launch(c, &sp, n, stream ? stream : (void *)c->stream);
 }
 
 int mosrx_steer_gather_dev(mosrx_ctx *c, const void *d_rec, const uint32_t *d_off, const uint16_t *d_len, uint32_t n,
@@ -2541,7 +2572,7 @@ int mosrx_steer_gather_side_dev(mosrx_ctx *c, const void *d_rec, const uint32_t 
 	sp.nb = 1;
 	sp.rec_bytes = (uint32_t)rec_bytes;
 	sp.total_tiles = (n + MOSRX_STEER_TILE - 1) / MOSRX_STEER_TILE;
-	return mosrx_launch_steer(&sp, stream ? stream : (void *)c->stream);
+	return steer_launch(c, &sp, n, stream ? stream : (void *)c->stream);
 }
 
 void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)

@@ -141,6 +141,8 @@ struct mosrx_ctx {
 	size_t steer_tmp_stride, steer_tmp_bytes;
 	size_t steer_tmp_scratch;        /*   the scratch part of a block, and the frames its gather part holds */
 	uint32_t steer_tmp_n;
+	uint32_t steer_one;              /* batches of at most this many frames steer in one launch (mosrx_set_steer_one); 0: off */
+	uint64_t steer_one_count;        /*   steer launches that did */
 };
 
 int mosrx__check_batch(const mosrx_batch *b, int dev);

@@ -70,13 +70,18 @@ typedef struct mosrx_sparams {
 	const mosrx_xdesc *xdesc; /* nb entries parallel to desc[] / gdesc[], or NULL */
 	mosrx_xdesc        xone;  /* the side arrays of `one` */
 	uint32_t           side;  /* 1 (with gather): the gather pass is its side form, over xdesc[] or xone */
+	uint32_t           fused; /* 1: one launch, one workgroup per batch (every n <= MOSRX_STEER_ONE_MAX);
+	                           * hist and tile_base unused, hist may be NULL */
 } mosrx_sparams;
 
 /* The three launches (histogram, scan, scatter) on `stream` (a hipStream_t);
  * 0, -EINVAL or -EIO.  Allocates nothing.  gather == 0 is the plain scatter
  * whatever gdesc / gone hold; with gather the single-batch form's pointers are
  * checked here (-EINVAL), a table's by whoever filled it.  side without gather
- * is -EINVAL; side == 0 is the gather form whatever xdesc / xone hold. */
+ * is -EINVAL; side == 0 is the gather form whatever xdesc / xone hold.
+ * With `fused` the one launch of mosrx_steer_one_kernel instead, in the form
+ * gather / side select: the same outputs, the same checks; the single-batch
+ * form's n above MOSRX_STEER_ONE_MAX is -EINVAL. */
 int mosrx_launch_steer(const mosrx_sparams *sp, void *stream);
 
 #ifdef __cplusplus

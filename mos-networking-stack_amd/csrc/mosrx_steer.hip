@@ -24,6 +24,10 @@
 // (3g below): the same positions, with the frame's record, offset and length
 // stored beside idx[pos].  Launches without them run the plain pass unchanged.
 //
+// With mosrx_sparams.fused the three launches are one kernel, one workgroup per
+// batch (mosrx_steer_one_kernel below): for batches of a tile or so, where the
+// launches' latency is the cost.  The five kernels above it are untouched by it.
+//
 // The key of frame i is byte rec_bytes - 3 of its record (mosrx_result.queue,
 // mosrx_result8.queue); it is read as the aligned dword that holds it, so a
 // wave's key loads are dword loads at a stride of 8 or 16 bytes: the same
@@ -378,6 +382,275 @@ __global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_gather_side_k
 	steer_gather_body<RB, true>(sp);
 }
 
+// ---- one launch: histogram, scan and scatter / gather in one workgroup --------
+// For batches small enough that launch latency, not the walk, is the cost
+// (mosrx_sparams.fused): workgroup blockIdx.x takes batch blockIdx.x whole, so
+// no workgroup needs another's counts, tile_base and hist are not used, and the
+// three phases are separated by __syncthreads() instead of launch boundaries.
+//   count  256 LDS bins over the batch's tiles, one atomic per distinct key per slice
+//   scan   the 8-step prefix over the bins -> qstart, and each queue's running position
+//   place  tile by tile in index order, the scatter / gather body's rows with the
+//          queue's running position as their base, then the position moves on by
+//          the tile's totals
+// A batch of one tile runs count and place from one load: its records (and
+// descriptors and side values) stay in registers across the scan, and the bins
+// are the column sums of s_row.  n, and with it every loop bound, comes from
+// the descriptor at entry and is uniform over the workgroup; every store is
+// under pos < n.  FORM: 0 idx only, 1 the gather outputs, 2 gather + side.
+#define STEER_ONE_PLAIN  0
+#define STEER_ONE_GATHER 1
+#define STEER_ONE_SIDE   2
+static_assert(MOSRX_STEER_ONE_MAX % MOSRX_STEER_TILE == 0 && MOSRX_STEER_ONE_MAX / MOSRX_STEER_TILE == 32u,
+              "the fused form's cap: 32 tiles");
+
+// One tile's frames in a lane's registers: STEER_SLICES frames, what the form gathers of each.
+template <uint32_t RB, int FORM> struct steer_one_tile {
+	typedef decltype(steer_rec<RB>::v) vec_t;
+	static constexpr uint32_t NG = FORM >= STEER_ONE_GATHER ? STEER_SLICES : 1u;
+	static constexpr uint32_t NS = FORM == STEER_ONE_SIDE ? STEER_SLICES : 1u;
+	uint32_t key[STEER_SLICES], rank[STEER_SLICES];
+	steer_rec<RB> r[NG];
+	uint32_t foff[NG], flen[NG];
+	uint32_t ffh[NS], fmt[NS], ti0[NS], ti1[NS], ti2[NS];
+};
+
+// Load tile `tl` of the batch (frames from `first`, this wave's slices) and leave
+// the slices' counts per key in s_row (zeroed by the caller, behind a barrier).
+template <uint32_t RB, int FORM>
+__device__ __forceinline__ void steer_one_load(steer_one_tile<RB, FORM> &f, const mosrx_sdesc &d, const mosrx_gdesc &g,
+                                               const mosrx_xdesc &x, uint32_t first, uint32_t row0, uint32_t lane,
+                                               uint32_t (*s_row)[MOSRX_STEER_BINS], bool descs, bool has_fh, bool has_mt,
+                                               bool has_ti)
+{
+	typedef typename steer_one_tile<RB, FORM>::vec_t vec_t;
+#pragma unroll
+	for (uint32_t s = 0; s < STEER_SLICES; s++) {
+		const uint32_t i = first + s * 64u + lane;
+		const bool valid = i < d.n;
+		if constexpr (FORM == STEER_ONE_PLAIN) {
+			f.key[s] = valid ? steer_key(d.rec, i, RB) : 0u;
+		} else {
+			f.r[s].v = vec_t{};
+			f.foff[s] = f.flen[s] = 0;
+			if constexpr (FORM == STEER_ONE_SIDE) {
+				f.ffh[s] = f.fmt[s] = 0;
+				f.ti0[s] = f.ti1[s] = f.ti2[s] = 0;
+			}
+			if (valid) {
+				f.r[s].v = *reinterpret_cast<const vec_t *>(d.rec + (uint64_t)i * RB);
+				if (descs) {
+					f.foff[s] = g.off[i];
+					f.flen[s] = g.len[i];
+				}
+				if constexpr (FORM == STEER_ONE_SIDE) {
+					if (has_fh)
+						f.ffh[s] = x.fhash[i];
+					if (has_mt)
+						f.fmt[s] = x.match[i];
+					if (has_ti) {
+						const uint32_t *w = reinterpret_cast<const uint32_t *>(x.tcpinfo) + (uint64_t)i * 3u;
+						f.ti0[s] = w[0];
+						f.ti1[s] = w[1];
+						f.ti2[s] = w[2];
+					}
+				}
+			}
+			f.key[s] = valid ? f.r[s].key() : 0u;
+		}
+		const uint64_t same = same_key_mask(f.key[s], valid);
+		f.rank[s] = lanes_below(same);
+		if (valid && f.rank[s] == 0)
+			s_row[row0 + s][f.key[s]] = (uint32_t)__builtin_popcountll(same);   // one writer per (row, key)
+	}
+}
+
+// Store the tile's frames at their positions (s_row: each slice's first position per key).
+template <uint32_t RB, int FORM>
+__device__ __forceinline__ void steer_one_store(const steer_one_tile<RB, FORM> &f, const mosrx_sdesc &d,
+                                                const mosrx_gdesc &g, const mosrx_xdesc &x, uint32_t first, uint32_t row0,
+                                                uint32_t lane, const uint32_t (*s_row)[MOSRX_STEER_BINS], bool descs,
+                                                bool has_fh, bool has_mt, bool has_ti)
+{
+	typedef typename steer_one_tile<RB, FORM>::vec_t vec_t;
+#pragma unroll
+	for (uint32_t s = 0; s < STEER_SLICES; s++) {
+		const uint32_t i = first + s * 64u + lane;
+		if (i < d.n) {
+			const uint32_t pos = s_row[row0 + s][f.key[s]] + f.rank[s];
+			if (pos < d.n) {   // as the three-launch passes: every store of the frame under the one guard
+				d.idx[pos] = i;
+				if constexpr (FORM >= STEER_ONE_GATHER) {
+					*reinterpret_cast<vec_t *>(g.qrec + (uint64_t)pos * RB) = f.r[s].v;
+					if (descs) {
+						g.qoff[pos] = f.foff[s];
+						g.qlen[pos] = (uint16_t)f.flen[s];
+					}
+				}
+				if constexpr (FORM == STEER_ONE_SIDE) {
+					if (has_fh)
+						x.qfhash[pos] = f.ffh[s];
+					if (has_mt)
+						x.qmatch[pos] = f.fmt[s];
+					if (has_ti) {
+						uint32_t *w = reinterpret_cast<uint32_t *>(x.qtcpinfo) + (uint64_t)pos * 3u;
+						w[0] = f.ti0[s];
+						w[1] = f.ti1[s];
+						w[2] = f.ti2[s];
+					}
+				}
+			}
+		}
+	}
+}
+
+// Lanes 0..255 hold their queue's count: write qstart (when given) and leave the
+// queue's first position in s_run[].  Every lane of the workgroup calls it (barriers).
+__device__ __forceinline__ void steer_one_scan(uint32_t t, uint32_t total, uint32_t *s_q, uint32_t *s_run,
+                                               uint32_t *qstart)
+{
+	const bool col = t < MOSRX_STEER_BINS;
+	if (col)
+		s_q[t] = total;
+	__syncthreads();
+	// inclusive prefix over the 256 queues (Hillis-Steele, 8 steps)
+#pragma unroll
+	for (uint32_t o = 1; o < MOSRX_STEER_BINS; o <<= 1) {
+		const uint32_t v = (col && t >= o) ? s_q[t - o] : 0u;
+		__syncthreads();
+		if (col)
+			s_q[t] += v;
+		__syncthreads();
+	}
+	if (col) {
+		const uint32_t incl = s_q[t];
+		s_run[t] = incl - total;
+		if (qstart) {
+			qstart[t] = incl - total;
+			if (t == MOSRX_STEER_BINS - 1u)
+				qstart[MOSRX_STEER_BINS] = incl;   // == n: every frame has one key
+		}
+	}
+}
+
+template <uint32_t RB, int FORM>
+__global__ __launch_bounds__(MOSRX_STEER_THREADS) void mosrx_steer_one_kernel(mosrx_sparams sp)
+{
+	// s_row as in the scatter pass; s_run[q]: the next position of queue q (the
+	// count phase's bins before the scan); s_q: the scan's working row
+	__shared__ uint32_t s_row[STEER_ROWS][MOSRX_STEER_BINS];
+	__shared__ uint32_t s_run[MOSRX_STEER_BINS];
+	__shared__ uint32_t s_q[MOSRX_STEER_BINS];
+	const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+	if (blockIdx.x >= (sp.desc ? sp.nb : 1u))
+		return;
+	mosrx_sdesc d;
+	mosrx_gdesc g = {};
+	mosrx_xdesc x = {};
+	if (sp.desc) {
+		d = sp.desc[blockIdx.x];
+		if constexpr (FORM >= STEER_ONE_GATHER)
+			g = sp.gdesc[blockIdx.x];
+		if constexpr (FORM == STEER_ONE_SIDE)
+			x = sp.xdesc[blockIdx.x];
+	} else {
+		d = sp.one;
+		if constexpr (FORM >= STEER_ONE_GATHER)
+			g = sp.gone;
+		if constexpr (FORM == STEER_ONE_SIDE)
+			x = sp.xone;
+	}
+	// all uniform over the workgroup: one descriptor per workgroup
+	const bool descs = FORM >= STEER_ONE_GATHER && g.qoff != nullptr;
+	const bool has_fh = FORM == STEER_ONE_SIDE && x.qfhash != nullptr, has_mt = FORM == STEER_ONE_SIDE && x.qmatch != nullptr;
+	const bool has_ti = FORM == STEER_ONE_SIDE && x.qtcpinfo != nullptr;
+	const uint32_t tiles = (d.n + MOSRX_STEER_TILE - 1u) / MOSRX_STEER_TILE;
+	const uint32_t row0 = wave * STEER_SLICES;
+	if (tiles == 0) {   // as the scan launch: an empty batch's qstart is 257 zeros, a NULL one is written nowhere
+		if (d.qstart && t < MOSRX_STEER_QSLOTS)
+			d.qstart[t] = 0;
+		return;
+	}
+	steer_one_tile<RB, FORM> f;
+	for (uint32_t j = t; j < STEER_ROWS * MOSRX_STEER_BINS; j += MOSRX_STEER_THREADS)
+		(&s_row[0][0])[j] = 0;
+	if (t < MOSRX_STEER_BINS)
+		s_run[t] = 0;
+	__syncthreads();
+	if (tiles == 1) {
+		// one tile: loaded once; the bins are s_row's column sums
+		steer_one_load<RB, FORM>(f, d, g, x, row0 * 64u, row0, lane, s_row, descs, has_fh, has_mt, has_ti);
+		__syncthreads();
+		uint32_t total = 0;
+		if (t < MOSRX_STEER_BINS) {
+#pragma unroll 8
+			for (uint32_t q = 0; q < STEER_ROWS; q++)
+				total += s_row[q][t];
+		}
+		steer_one_scan(t, total, s_q, s_run, d.qstart);
+		if (t < MOSRX_STEER_BINS) {   // (lane t wrote s_run[t] itself)
+			uint32_t run = s_run[t];
+#pragma unroll 8
+			for (uint32_t q = 0; q < STEER_ROWS; q++) {
+				const uint32_t v = s_row[q][t];
+				s_row[q][t] = run;
+				run += v;
+			}
+		}
+		__syncthreads();
+		steer_one_store<RB, FORM>(f, d, g, x, row0 * 64u, row0, lane, s_row, descs, has_fh, has_mt, has_ti);
+		return;
+	}
+	// count: the key dword of every frame, tile by tile
+	for (uint32_t tl = 0; tl < tiles; tl++) {
+		const uint32_t first = tl * MOSRX_STEER_TILE + row0 * 64u;
+#pragma unroll
+		for (uint32_t s = 0; s < STEER_SLICES; s++) {
+			const uint32_t i = first + s * 64u + lane;
+			const bool valid = i < d.n;
+			const uint32_t key = valid ? steer_key(d.rec, i, RB) : 0u;
+			const uint64_t same = same_key_mask(key, valid);
+			if (valid && lanes_below(same) == 0)
+				atomicAdd(&s_run[key], (uint32_t)__builtin_popcountll(same));
+		}
+	}
+	__syncthreads();
+	steer_one_scan(t, t < MOSRX_STEER_BINS ? s_run[t] : 0u, s_q, s_run, d.qstart);
+	// place: s_row is zero on entry to every round
+	for (uint32_t tl = 0; tl < tiles; tl++) {
+		const uint32_t first = tl * MOSRX_STEER_TILE + row0 * 64u;
+		steer_one_load<RB, FORM>(f, d, g, x, first, row0, lane, s_row, descs, has_fh, has_mt, has_ti);
+		__syncthreads();
+		if (t < MOSRX_STEER_BINS) {
+			uint32_t run = s_run[t];
+#pragma unroll 8
+			for (uint32_t q = 0; q < STEER_ROWS; q++) {
+				const uint32_t v = s_row[q][t];
+				s_row[q][t] = run;
+				run += v;
+			}
+			s_run[t] = run;   // the queue's position after this tile
+		}
+		__syncthreads();
+		steer_one_store<RB, FORM>(f, d, g, x, first, row0, lane, s_row, descs, has_fh, has_mt, has_ti);
+		__syncthreads();
+		for (uint32_t j = t; j < STEER_ROWS * MOSRX_STEER_BINS; j += MOSRX_STEER_THREADS)
+			(&s_row[0][0])[j] = 0;
+		__syncthreads();
+	}
+}
+
+template <uint32_t RB>
+static void steer_one_launch(const mosrx_sparams *sp, hipStream_t s)
+{
+	const dim3 grid(sp->desc ? sp->nb : 1u), block(MOSRX_STEER_THREADS);
+	if (!sp->gather)
+		hipLaunchKernelGGL((mosrx_steer_one_kernel<RB, STEER_ONE_PLAIN>), grid, block, 0, s, *sp);
+	else if (!sp->side)
+		hipLaunchKernelGGL((mosrx_steer_one_kernel<RB, STEER_ONE_GATHER>), grid, block, 0, s, *sp);
+	else
+		hipLaunchKernelGGL((mosrx_steer_one_kernel<RB, STEER_ONE_SIDE>), grid, block, 0, s, *sp);
+}
+
 static int gather_ok(const mosrx_sparams *sp)
 {
 	const mosrx_gdesc *g = &sp->gone;
@@ -413,14 +686,23 @@ static int side_ok(const mosrx_sparams *sp)
 extern "C" int mosrx_launch_steer(const mosrx_sparams *sp, void *stream)
 {
 	const hipStream_t s = (hipStream_t)stream;
-	if (!sp || !sp->hist || (sp->rec_bytes != 8u && sp->rec_bytes != 16u) || (sp->desc && sp->nb == 0))
+	if (!sp || (!sp->hist && !sp->fused) || (sp->rec_bytes != 8u && sp->rec_bytes != 16u) || (sp->desc && sp->nb == 0))
 		return -EINVAL;
 	if (sp->gather && !gather_ok(sp))
 		return -EINVAL;
 	if (sp->side && !side_ok(sp))
 		return -EINVAL;
+	if (sp->fused && !sp->desc && sp->one.n > MOSRX_STEER_ONE_MAX)   /* (a table's batches: whoever filled it) */
+		return -EINVAL;
 	if (sp->total_tiles == 0 && !sp->desc)
 		return 0;
+	if (sp->fused) {
+		if (sp->rec_bytes == 8u)
+			steer_one_launch<8u>(sp, s);
+		else
+			steer_one_launch<16u>(sp, s);
+		return hipGetLastError() == hipSuccess ? 0 : -EIO;
+	}
 	if (sp->total_tiles)
 		hipLaunchKernelGGL(mosrx_steer_hist_kernel, dim3(sp->total_tiles), dim3(MOSRX_STEER_THREADS), 0, s, *sp);
 	hipLaunchKernelGGL(mosrx_steer_scan_kernel, dim3(sp->desc ? sp->nb : 1u), dim3(SCAN_THREADS), 0, s, *sp);

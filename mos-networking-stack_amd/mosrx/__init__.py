@@ -109,6 +109,7 @@ OP_STEER_GATHER = 8    # MOSRX_OP_STEER_GATHER: ... with the scatter launch in i
 OP_STEER_GATHER_SIDE = 9   # MOSRX_OP_STEER_GATHER_SIDE: ... in its side form (arg = rec_bytes | SIDE_* bits << 8)
 SIDE_FHASH, SIDE_MATCH, SIDE_TCPINFO = 1, 2, 4   # MOSRX_SIDE_*
 STEER_QSLOTS = 257     # MOSRX_STEER_QSLOTS: qstart entries per batch
+STEER_ONE_MAX = 65536  # MOSRX_STEER_ONE_MAX: the most frames per batch the one-launch steer form takes
 # include/mosrx.h mosrx_tx_check: the TX checks of a frame, the frame untouched
 TX_CHECK_DTYPE = np.dtype([("ip_check", "<u2"), ("tcp_check", "<u2"), ("what", "u1"), ("ihl", "u1"),
                            ("pad", "<u2")])
@@ -381,6 +382,12 @@ def lib():
                                                 P]),
             "mosrx_queue_set_steer_gather_side": (I, [P, P] + [C.POINTER(P)] * 7),
             "mosrx_slot_steer_gather_side": (I, [P, I] + [C.POINTER(P)] * 8),
+            "mosrx_set_steer_one": (I, [P, U32]),
+            "mosrx_get_steer_one": (U32, [P]),
+            "mosrx_steer_one_count": (U64, [P]),
+            "mosrx_gpu_module_steer_one_count": (U64, [P]),
+            "mosrx_gpu_module_set_steer_one": (I, [C.c_int32]),
+            "mosrx_gpu_module_get_steer_one": (C.c_int32, []),
             "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
             "mosrx_hub_endpoint": (P, [P, U32]),
             "mosrx_hub_stats_get": (I, [P, P]),
@@ -949,6 +956,18 @@ class Context:
         pinned input run copy-free."""
         _chk(lib().mosrx_set_direct(self.handle, int(max_bytes), int(max_frames)), "mosrx_set_direct")
 
+    def set_steer_one(self, max_frames: int) -> None:
+        """mosrx_set_steer_one: steer launches whose batches all have at most
+        max_frames frames (up to STEER_ONE_MAX) run as one kernel; 0: the three launches."""
+        _chk(lib().mosrx_set_steer_one(self.handle, int(max_frames)), "mosrx_set_steer_one")
+
+    def get_steer_one(self) -> int:
+        return int(lib().mosrx_get_steer_one(self.handle))
+
+    def steer_one_count(self) -> int:
+        """mosrx_steer_one_count: this context's steer launches that took the one-launch form."""
+        return int(lib().mosrx_steer_one_count(self.handle))
+
     def slot_direct(self, slot: int) -> bool:
         """mosrx_slot_direct: the slot's last group submit ran copy-free."""
         rc = lib().mosrx_slot_direct(self.handle, slot)
@@ -1220,7 +1239,8 @@ class GpuBackend:
                  ngpu: int = 1, bpf=None, group: int = 1, tcpinfo: bool = False, tx_batch: int = 64,
                  timing: bool = False, flowhash: bool = False, tx_csum: bool = False, compact: bool = False,
                  group_bytes: int = 0, group_max_us: int = 0, direct_kb: int | None = None,
-                 direct_frames: int | None = None, module_lib=None, steer: bool | int = False):
+                 direct_frames: int | None = None, module_lib=None, steer: bool | int = False,
+                 steer_one: int = 0):
         self.L = L = module_lib or lib()
         cfg = ModuleCfg()
         L.mosrx_gpu_module_cfg_default(C.byref(cfg))
@@ -1251,6 +1271,9 @@ class GpuBackend:
             cfg.bpf_progs = C.addressof(self._bpf[0])
             cfg.bpf_nprog = len(bpf)
         _chk(L.mosrx_gpu_module_configure(C.byref(cfg)), "mosrx_gpu_module_configure")
+        # steered groups of batches up to this many frames: one steer launch (0: never; always set,
+        # so a backend does not inherit an earlier one's)
+        _chk(L.mosrx_gpu_module_set_steer_one(int(steer_one)), "mosrx_gpu_module_set_steer_one")
         self.nif = len(sources)
         self.sources = list(sources)
         self.m = IoModuleFunc.in_dll(L, "gpu_module_func")
@@ -1266,6 +1289,10 @@ class GpuBackend:
         self._send = _SENDFN(self.m.send_pkts)
         if timing:
             _chk(L.mosrx_gpu_module_set_timing(self.ctx, 1), "mosrx_gpu_module_set_timing")
+
+    def steer_one_count(self) -> int:
+        """mosrx_gpu_module_steer_one_count: steered groups that took the one-launch form."""
+        return int(self.L.mosrx_gpu_module_steer_one_count(self.ctx))
 
     def recv_pkts(self, ifidx: int = 0) -> int:
         return self._recv(self.ctx, ifidx)
