@@ -374,6 +374,100 @@ uint32_t mosrx_get_steer_one(const mosrx_ctx *c);
 /* Steer launches of this context that took the one-launch form so far. */
 uint64_t mosrx_steer_one_count(const mosrx_ctx *c);
 
+/* ---- forwarding: the frames a forward = 1 stack passes on -------------------- */
+/* What ProcessPacket does with a frame it does not keep: ForwardIPPacket
+ * (ip_out.c:39-110: GetOutputInterface's longest-prefix walk, ip_out.c:11-37;
+ * GetDestinationHWaddr's, arp.c:88-119; EthernetOutput's 14-byte header,
+ * eth_out.c:62-102; a memcpy of the IP packet) or ForwardEthernetFrame
+ * (eth_out.c:104-134), over a classified batch: a plan record per frame, then
+ * the TX frames mOS would have put on the wire, byte for byte, in arrival
+ * order.  Stateless per launch: the tables are the fields mOS holds after it
+ * parsed mos.conf, taken verbatim (addresses in network order as struct
+ * route_entry / struct _arp_entry keep them; no mask is recomputed here). */
+#define MOSRX_FWD_MAX_ROUTES  128    /* MAX_ROUTE_ENTRY */
+#define MOSRX_FWD_MAX_ARP     1024   /* MAX_ARPENTRY */
+#define MOSRX_FWD_MAX_NETDEVS 16
+typedef struct mosrx_fwd_route {
+	uint32_t mask, masked_ip;
+	int32_t  prefix, nif;            /* nif: an index into the netdevs */
+} mosrx_fwd_route;
+typedef struct mosrx_fwd_arp {
+	uint32_t ip, mask, masked_ip;
+	int32_t  prefix;
+	uint8_t  haddr[6];
+	uint8_t  pad[2];
+} mosrx_fwd_arp;
+typedef struct mosrx_fwd_tables {
+	uint32_t num_routes;             /* <= MOSRX_FWD_MAX_ROUTES */
+	uint32_t num_arp;                /* <= MOSRX_FWD_MAX_ARP */
+	uint32_t num_netdevs;            /* <= MOSRX_FWD_MAX_NETDEVS */
+	int32_t  has_nic_fwd;            /* g_config.mos->nic_forward_table != NULL */
+	int8_t   nic_fwd[MOSRX_FWD_MAX_NETDEVS];   /* nic_fwd_table[in_ifidx]: an output netdev or -1 */
+	uint8_t  netdev_haddr[MOSRX_FWD_MAX_NETDEVS][6];
+	mosrx_fwd_route routes[MOSRX_FWD_MAX_ROUTES];
+	mosrx_fwd_arp   arp[MOSRX_FWD_MAX_ARP];
+} mosrx_fwd_tables;
+
+/* The plan of one frame, 8 bytes. */
+enum {
+	MOSRX_FWD_NONE     = 0,  /* not forwarded (mosrx_mos_forwards' rule; TRUNCATED never is) */
+	MOSRX_FWD_IP       = 1,  /* ForwardIPPacket sends 14 + ntohs(tot_len) bytes */
+	MOSRX_FWD_ETH      = 2,  /* ForwardEthernetFrame sends the frame as captured */
+	MOSRX_FWD_NO_ROUTE = 3,  /* GetOutputInterface found no route */
+	MOSRX_FWD_NO_ARP   = 4,  /* GetDestinationHWaddr found no entry (forward = 1: no ARP request, ip_out.c:69) */
+	MOSRX_FWD_NO_NIC   = 5   /* no nic_forward_table, or its entry is -1 (non-IPv4 frames) */
+};
+typedef struct mosrx_fwd {
+	uint16_t tx_len;      /* bytes sent; 0 unless kind is IP or ETH */
+	int8_t   out_ifidx;   /* the output netdev (IP, ETH, NO_ARP), else -1 */
+	uint8_t  kind;        /* MOSRX_FWD_* */
+	uint16_t arp_idx;     /* the ARP entry GetDestinationHWaddr picked; 0xFFFF: none (the frame keeps its h_dest) */
+	uint16_t reserved;    /* 0 */
+} mosrx_fwd;
+
+/* Validate the tables and upload one packed device copy for the context:
+ * -EINVAL when a count is over its limit, a route's nif or a nic_fwd entry
+ * (other than -1) is outside the netdevs.  NULL clears them.  In effect for
+ * launches submitted after it returns; launches already submitted keep the
+ * copy they were given (a device copy is rewritten only after they drained). */
+int  mosrx_fwd_set(mosrx_ctx *c, const mosrx_fwd_tables *t);
+/* 1 when an end-host socket listens (mtcp->listener): TCP frames of flows
+ * without a stream are then answered, not forwarded (tcp.c:453-510).  0 at open. */
+int  mosrx_fwd_set_listener(mosrx_ctx *c, int listener);
+/* Plan a device-resident batch from its n records of rec_bytes (16 or 8) as a
+ * classify call on the same stream left them, under the context's forward /
+ * num_msp and the listener flag; in_ifidx is the batch's input netdev.  One
+ * launch into d_plan[n] (8-byte aligned).  Allocates nothing, graph-capturable.
+ * -EINVAL: NULL or misaligned pointer, rec_bytes, in_ifidx outside
+ * 0 .. MOSRX_FWD_MAX_NETDEVS - 1; -ENOENT: no tables set.  n == 0 returns 0
+ * and launches nothing. */
+int  mosrx_fwd_plan_dev(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, int in_ifidx,
+                        mosrx_fwd *d_plan, void *stream);
+/* Build the TX frames of a planned batch, in arrival order: sent frame j
+ * (kind IP or ETH) at tx_off[j] = 16 k + 2 (the library's staging convention:
+ * the IP header on a 16-byte boundary), k the exclusive scan of
+ * ceil((2 + tx_len) / 16) over the sent frames.  An IP frame is h_dest (the
+ * ARP entry's, or its own on the nic_forward_table path), h_source = the output
+ * netdev's haddr, its ethertype, then tx_len - 14 bytes from frame byte 14;
+ * an ETH frame is copied unchanged.
+ *   d_tx_frames[tx_cap]  16-byte aligned; only frame bytes are written
+ *   d_tx_off / d_tx_len / d_tx_nif / d_tx_src [m]   src: the frame's index in the batch
+ *   d_tx_count[2]        {m, frames dropped for lack of room}
+ * A frame whose padded end passes tx_cap is not written and counted dropped,
+ * and so is every later one.  Entries past m and bytes past the last frame
+ * are left untouched; the four arrays need room for n entries.  Three launches
+ * (totals, scan, copy) on one stream; allocates nothing, graph-capturable.
+ * -EINVAL: NULL or misaligned pointer, scratch under mosrx_fwd_scratch_bytes(n);
+ * -ENOENT: no tables set. */
+int  mosrx_fwd_build_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint8_t *d_tx_frames,
+                         uint64_t tx_cap, uint32_t *d_tx_off, uint16_t *d_tx_len, int8_t *d_tx_nif,
+                         uint32_t *d_tx_src, uint32_t *d_tx_count, void *d_scratch, size_t scratch_bytes,
+                         void *stream);
+/* Scratch a build of n frames needs (no GPU needed; never 0, non-decreasing in
+ * n; 16-byte aligned at the call), and the frames one workgroup takes. */
+size_t   mosrx_fwd_scratch_bytes(uint32_t n);
+uint32_t mosrx_fwd_tile(void);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned
@@ -536,7 +630,12 @@ enum { MOSRX_OP_CLASSIFY = 0, MOSRX_OP_CLASSIFY_FH = 1, MOSRX_OP_BPF = 2, MOSRX_
                                   * (device resident) are gathered too, into outputs of the timing call's own */,
        MOSRX_OP_STEER_GATHER_SIDE = 9 /* MOSRX_OP_STEER_GATHER in its side form: `arg` = rec_bytes | which << 8, which
                                        * the MOSRX_SIDE_* arrays to gather (0: all three); side sources and outputs
-                                       * are the timing call's own */ };
+                                       * are the timing call's own */,
+       MOSRX_OP_FWD_PLAN = 10 /* the forwarding plan over records already made: out[i] the records of batch i, aux[i]
+                               * its mosrx_fwd plan array, `arg` = rec_bytes | in_ifidx << 8 */,
+       MOSRX_OP_FWD = 11 /* MOSRX_OP_FWD_PLAN followed by the build (four launches: -ENOTSUP from
+                          * mosrx_time_op_dispatch); the TX outputs and scratch are the timing call's own, tx_cap
+                          * what the batch's frames need at most */ };
 int  mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t nb, void *const *out,
                    void *const *aux, uint32_t iters, uint32_t nstreams, float *total_ms, float *avg_kernel_ms);
 /* The kernel's own duration, averaged over `iters` back-to-back launches on

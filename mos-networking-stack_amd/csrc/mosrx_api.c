@@ -297,6 +297,10 @@ void mosrx_close(mosrx_ctx *c)
 	mosrx__bpf_jit_free(c);   /* (joins the compile thread; launches drained above) */
 	if (c->d_tables) hipFree(c->d_tables);
 	if (c->steer_tmp) hipFree(c->steer_tmp);
+	if (c->fwd_tmp) hipFree(c->fwd_tmp);
+	for (i = 0; i < MOSRX_FWD_POOL; i++)
+		if (c->d_fwd_pool[i])
+			hipFree(c->d_fwd_pool[i]);
 	for (i = 0; i < MOSRX_BPF_POOL; i++)
 		if (c->d_bpf_pool[i])
 			hipFree(c->d_bpf_pool[i]);
@@ -1827,6 +1831,40 @@ static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
 	return 0;
 }
 
+/* MOSRX_OP_FWD's TX outputs + scratch: one block for the context stream and
+ * one per timing stream, sized for the largest batch (each part rounded to
+ * 256 bytes): tx_frames with room for every frame of the batch sent whole
+ * (its frame bytes + 32 a frame), tx_off, tx_src, tx_len, tx_nif, tx_count,
+ * scratch. */
+#define OP_IS_FWD(op) ((op) == MOSRX_OP_FWD_PLAN || (op) == MOSRX_OP_FWD)
+static int fwd_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
+{
+	uint32_t i, maxn = 0;
+	uint64_t maxb = 0;
+	size_t stride, bytes;
+	for (i = 0; i < nb; i++) {
+		maxn = b[i].n > maxn ? b[i].n : maxn;
+		maxb = b[i].frames_bytes > maxb ? b[i].frames_bytes : maxb;
+	}
+	c->fwd_tmp_n = maxn;
+	c->fwd_tmp_cap = STEER_TMP_RND(maxb + 32ull * maxn);
+	stride = c->fwd_tmp_cap + 2 * STEER_TMP_RND((size_t)maxn * 4) + STEER_TMP_RND((size_t)maxn * 2) +
+	         STEER_TMP_RND(maxn) + 256 + STEER_TMP_RND(mosrx_fwd_scratch_bytes(maxn));
+	bytes = stride * (MOSRX_MAX_STREAMS + 1);
+	if (bytes > c->fwd_tmp_bytes) {
+		HIPCHK(hipDeviceSynchronize());
+		if (c->fwd_tmp)
+			hipFree(c->fwd_tmp);
+		c->fwd_tmp = NULL;
+		c->fwd_tmp_bytes = 0;
+		if (hipMalloc((void **)&c->fwd_tmp, bytes) != hipSuccess)
+			return -ENOMEM;
+		c->fwd_tmp_bytes = bytes;
+	}
+	c->fwd_tmp_stride = stride;
+	return 0;
+}
+
 /* One enqueue of operation `op` on batch b (see mosrx_time_op). */
 static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out, void *aux, hipStream_t s)
 {
@@ -1878,6 +1916,27 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 		}
 		return mosrx_steer_gather_dev(c, out, b->off, b->len, b->n, rb, (uint32_t *)aux, (uint32_t *)blk, qrec,
 		                              (uint32_t *)qoff, (uint16_t *)qlen, blk + STEER_TMP_QS, c->steer_tmp_scratch, s);
+	}
+	case MOSRX_OP_FWD_PLAN:
+	case MOSRX_OP_FWD: {
+		uint32_t k = 0;
+		uint8_t *blk, *toff, *tsrc, *tlen, *tnif, *tcnt, *scr;
+		const size_t w = STEER_TMP_RND((size_t)c->fwd_tmp_n * 4);
+		int rc = mosrx_fwd_plan_dev(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, s);
+		if (rc || op == MOSRX_OP_FWD_PLAN)
+			return rc;
+		while (k < c->nxs && c->xs[k] != s)
+			k++;
+		blk = c->fwd_tmp + (size_t)(k < c->nxs ? k + 1 : 0) * c->fwd_tmp_stride;
+		toff = blk + c->fwd_tmp_cap;
+		tsrc = toff + w;
+		tlen = tsrc + w;
+		tnif = tlen + STEER_TMP_RND((size_t)c->fwd_tmp_n * 2);
+		tcnt = tnif + STEER_TMP_RND(c->fwd_tmp_n);
+		scr = tcnt + 256;
+		return mosrx_fwd_build_dev(c, b, (const mosrx_fwd *)aux, blk, c->fwd_tmp_cap, (uint32_t *)toff, (uint16_t *)tlen,
+		                           (int8_t *)tnif, (uint32_t *)tsrc, (uint32_t *)tcnt, scr,
+		                           STEER_TMP_RND(mosrx_fwd_scratch_bytes(c->fwd_tmp_n)), s);
 	}
 	default: return -EINVAL;
 	}
@@ -1965,14 +2024,18 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 {
 	int rc;
 	if (!c || !b || nb == 0 || iters == 0 || nstreams == 0 || nstreams > MOSRX_MAX_STREAMS ||
-	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER_GATHER_SIDE || (op != MOSRX_OP_TX_CSUM && !out) ||
-	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op)) &&
-	     !aux) ||
+	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD || (op != MOSRX_OP_TX_CSUM && !out) ||
+	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
+	      OP_IS_FWD(op)) && !aux) ||
+	    (OP_IS_FWD(op) && (((arg & 0xFF) != 8 && (arg & 0xFF) != 16) || (arg >> 8) < 0 ||
+	                       (arg >> 8) >= MOSRX_FWD_MAX_NETDEVS)) ||
 	    ((op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && arg != 8 && arg != 16) ||
 	    (op == MOSRX_OP_STEER_GATHER_SIDE && (((arg & 0xFF) != 8 && (arg & 0xFF) != 16) || (arg >> 8) < 0 || (arg >> 8) > 7)))
 		return -EINVAL;
 	HIPCHK(hipSetDevice(c->device));
 	if (OP_IS_STEER(op) && (rc = steer_tmp_reserve(c, b, nb)))
+		return rc;
+	if (op == MOSRX_OP_FWD && (rc = fwd_tmp_reserve(c, b, nb)))
 		return rc;
 	if (total_ms && (rc = time_streams(c, op, arg, b, nb, out, aux, iters, nstreams, total_ms)))
 		return rc;
@@ -2036,12 +2099,12 @@ int mosrx_time_op_dispatch(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, 
                            void *const *aux, uint32_t iters, float *avg_ms)
 {
 	struct op_run r = {op, arg, b, nb, out, aux};
-	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_STEER_GATHER_SIDE ||
+	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD ||
 	    (op != MOSRX_OP_TX_CSUM && !out) ||
-	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op)) &&
-	     !aux))
+	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
+	      OP_IS_FWD(op)) && !aux))
 		return -EINVAL;
-	if (OP_IS_STEER(op))   /* three launches: no single dispatch to stamp */
+	if (OP_IS_STEER(op) || OP_IS_FWD(op))   /* several launches, or none of mosrx_kernels.hip: no dispatch to stamp */
 		return -ENOTSUP;
 	/* (the BPF ops are one launch with the fused kernel / the set's own kernel;
 	 * classify + the set's kernel, two, is refused by the launch count) */
@@ -2626,4 +2689,175 @@ int mosrx_time_queue(mosrx_ctx *c, mosrx_queue *const *q, uint32_t nq, uint32_t 
 		*avg_kernel_ms = (float)(tot / (i ? i : 1));
 	}
 	return 0;
+}
+
+/* ---- forwarding (csrc/mosrx_fwd.hip) ---------------------------------------- */
+
+size_t mosrx_fwd_scratch_bytes(uint32_t n)
+{
+	const size_t tiles = ((size_t)n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+	return (tiles ? tiles : 1) * MOSRX_FWD_ROW;
+}
+
+uint32_t mosrx_fwd_tile(void) { return MOSRX_FWD_TILE; }
+
+int mosrx_fwd_set_listener(mosrx_ctx *c, int listener)
+{
+	if (!c)
+		return -EINVAL;
+	c->fwd_listener = listener != 0;
+	return 0;
+}
+
+/* The tables go to the next buffer of a pool, as the BPF instruction buffers
+ * do (bpf_api.c stage_insns): launches submitted earlier may still read the
+ * copy they were given, so a buffer is written again only after those launches
+ * drained, and only if a launch may have read it since its last write. */
+int mosrx_fwd_set(mosrx_ctx *c, const mosrx_fwd_tables *t)
+{
+	mosrx_fwd_dev *h;
+	uint32_t i, k;
+	int rc;
+	if (!c)
+		return -EINVAL;
+	if (!t) {
+		c->d_fwd = NULL;
+		return 0;
+	}
+	if (t->num_routes > MOSRX_FWD_MAX_ROUTES || t->num_arp > MOSRX_FWD_MAX_ARP ||
+	    t->num_netdevs > MOSRX_FWD_MAX_NETDEVS)
+		return -EINVAL;
+	for (i = 0; i < t->num_routes; i++)
+		if (t->routes[i].nif < 0 || (uint32_t)t->routes[i].nif >= t->num_netdevs)
+			return -EINVAL;
+	for (i = 0; t->has_nic_fwd && i < MOSRX_FWD_MAX_NETDEVS; i++)
+		if (t->nic_fwd[i] != -1 && (t->nic_fwd[i] < 0 || (uint32_t)t->nic_fwd[i] >= t->num_netdevs))
+			return -EINVAL;
+	if (!(h = calloc(1, sizeof(*h))))
+		return -ENOMEM;
+	h->num_routes = t->num_routes;
+	h->num_arp = t->num_arp;
+	h->num_netdevs = t->num_netdevs;
+	h->has_nic_fwd = t->has_nic_fwd != 0;
+	memcpy(h->nic_fwd, t->nic_fwd, sizeof(h->nic_fwd));
+	for (i = 0; i < MOSRX_FWD_MAX_NETDEVS; i++)
+		memcpy(h->netdev_haddr[i], t->netdev_haddr[i], 6);
+	for (i = 0; i < t->num_routes; i++) {
+		h->r_mask[i] = t->routes[i].mask;
+		h->r_masked[i] = t->routes[i].masked_ip;
+		h->r_prefix[i] = t->routes[i].prefix;
+		h->r_nif[i] = t->routes[i].nif;
+	}
+	for (i = 0; i < t->num_arp; i++) {
+		/* prefix 1 is GetDestinationHWaddr's exact-address form (arp.c:102-106) */
+		const int exact = t->arp[i].prefix == 1;
+		h->a_mask[i] = exact ? 0xFFFFFFFFu : t->arp[i].mask;
+		h->a_masked[i] = exact ? t->arp[i].ip : t->arp[i].masked_ip;
+		h->a_prefix[i] = t->arp[i].prefix;
+		memcpy(h->a_haddr[i], t->arp[i].haddr, 6);
+	}
+	rc = 0;
+	k = c->fwd_pool_next;
+	if (hipSetDevice(c->device) != hipSuccess)
+		rc = -EIO;
+	if (!rc && !c->d_fwd_pool[k] && hipMalloc((void **)&c->d_fwd_pool[k], sizeof(*h)) != hipSuccess)
+		rc = -ENOMEM;
+	if (!rc && c->fwd_pool_used[k] && !(rc = mosrx__drain(c)))
+		memset(c->fwd_pool_used, 0, sizeof(c->fwd_pool_used));
+	if (!rc && hipMemcpy(c->d_fwd_pool[k], h, sizeof(*h), hipMemcpyHostToDevice) != hipSuccess)
+		rc = -EIO;
+	free(h);
+	if (rc)
+		return rc;
+	c->d_fwd = c->d_fwd_pool[k];
+	c->fwd_pool_next = (k + 1) % MOSRX_FWD_POOL;
+	return 0;
+}
+
+/* A launch that reads the installed tables is about to go to stream s. */
+static void fwd_mark_used(mosrx_ctx *c)
+{
+	c->fwd_pool_used[(c->fwd_pool_next + MOSRX_FWD_POOL - 1) % MOSRX_FWD_POOL] = 1;
+}
+
+static int fwd_batch(const mosrx_ctx *c, const mosrx_batch *b, mosrx_fparams *fp)
+{
+	int rc;
+	if ((rc = mosrx__check_batch(b, 1)))
+		return rc;
+	if (b->n && ((((uintptr_t)b->off) & 3) || (((uintptr_t)b->len) & 1)))
+		return -EINVAL;
+	memset(fp, 0, sizeof(*fp));
+	fp->frames = b->frames;
+	fp->off = b->off;
+	fp->len = b->len;
+	fp->frames_bytes = (uint32_t)b->frames_bytes;
+	fp->n = b->n;
+	fp->tab = c->d_fwd;
+	return 0;
+}
+
+int mosrx_fwd_plan_dev(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, int in_ifidx,
+                       mosrx_fwd *d_plan, void *stream)
+{
+	mosrx_fparams fp;
+	hipStream_t s;
+	int rc;
+	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || (rec_bytes != 8 && rec_bytes != 16) || in_ifidx < 0 ||
+	    in_ifidx >= MOSRX_FWD_MAX_NETDEVS || (b->n && (!d_rec || ((uintptr_t)d_rec & (uintptr_t)(rec_bytes - 1)))))
+		return -EINVAL;
+	if ((rc = fwd_batch(c, b, &fp)))
+		return rc;
+	if (!c->d_fwd)
+		return -ENOENT;
+	if (b->n == 0)
+		return 0;
+	fp.rec = (const uint8_t *)d_rec;
+	fp.rec_bytes = (uint32_t)rec_bytes;
+	fp.in_ifidx = in_ifidx;
+	fp.plan = d_plan;
+	fp.forward = c->params.forward;
+	fp.num_msp = c->params.num_msp;
+	fp.listener = c->fwd_listener;
+	s = stream ? (hipStream_t)stream : c->stream;
+	HIPCHK(hipSetDevice(c->device));
+	fwd_mark_used(c);
+	rc = mosrx_launch_fwd_plan(&fp, (void *)s);
+	mosrx__note_stream(c, s);   /* (after the launch: its event covers it) */
+	return rc;
+}
+
+int mosrx_fwd_build_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint8_t *d_tx_frames,
+                        uint64_t tx_cap, uint32_t *d_tx_off, uint16_t *d_tx_len, int8_t *d_tx_nif,
+                        uint32_t *d_tx_src, uint32_t *d_tx_count, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+	mosrx_fparams fp;
+	hipStream_t s;
+	int rc;
+	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || !d_tx_frames || ((uintptr_t)d_tx_frames & 15) || !d_tx_off ||
+	    ((uintptr_t)d_tx_off & 3) || !d_tx_len || ((uintptr_t)d_tx_len & 1) || !d_tx_nif || !d_tx_src ||
+	    ((uintptr_t)d_tx_src & 3) || !d_tx_count || ((uintptr_t)d_tx_count & 3) || !d_scratch ||
+	    ((uintptr_t)d_scratch & 15) || scratch_bytes < mosrx_fwd_scratch_bytes(b->n))
+		return -EINVAL;
+	if ((rc = fwd_batch(c, b, &fp)))
+		return rc;
+	if (!c->d_fwd)
+		return -ENOENT;
+	fp.plan = (mosrx_fwd *)d_plan;
+	/* tx_off is a u32: room past 4 GiB is never used */
+	fp.cap_units = (uint32_t)((tx_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : tx_cap) / 16);
+	fp.tx = d_tx_frames;
+	fp.tx_off = d_tx_off;
+	fp.tx_len = d_tx_len;
+	fp.tx_nif = d_tx_nif;
+	fp.tx_src = d_tx_src;
+	fp.tx_count = d_tx_count;
+	fp.scratch = (uint32_t *)d_scratch;
+	fp.tiles = (b->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+	s = stream ? (hipStream_t)stream : c->stream;
+	HIPCHK(hipSetDevice(c->device));
+	fwd_mark_used(c);
+	rc = mosrx_launch_fwd_build(&fp, (void *)s);
+	mosrx__note_stream(c, s);
+	return rc;
 }

@@ -10,11 +10,13 @@
 
 #include "mosrx_internal.h"
 #include "mosrx_steer.h"
+#include "mosrx_fwd.h"
 
 #define HIPCHK(x) do { if ((x) != hipSuccess) return -EIO; } while (0)
 
 #define MOSRX_BPF_JIT_CACHE 16   /* compiled program sets kept per context */
 #define MOSRX_BPF_POOL 8         /* device buffers the interpreter's instructions rotate over */
+#define MOSRX_FWD_POOL 4         /* device copies the forwarding tables rotate over */
 
 /* The fused classify + BPF kernels of a compiled set (bpf_jit.c k_fused_main):
  * one batch as the stream tile (non-temporal / cached tails) or the SMALL tile,
@@ -143,6 +145,20 @@ struct mosrx_ctx {
 	uint32_t steer_tmp_n;
 	uint32_t steer_one;              /* batches of at most this many frames steer in one launch (mosrx_set_steer_one); 0: off */
 	uint64_t steer_one_count;        /*   steer launches that did */
+	/* forwarding (mosrx_fwd_set): the installed tables' device copy (NULL: none),
+	 * one of a pool under the BPF instruction buffers' discipline -- each set goes
+	 * to the next buffer, and a buffer a launch may have read is rewritten only
+	 * after mosrx__drain */
+	mosrx_fwd_dev *d_fwd;
+	mosrx_fwd_dev *d_fwd_pool[MOSRX_FWD_POOL];
+	int fwd_pool_used[MOSRX_FWD_POOL];
+	uint32_t fwd_pool_next;
+	uint32_t fwd_listener;           /* mosrx_fwd_set_listener */
+	/* MOSRX_OP_FWD's own TX outputs + scratch, one block of fwd_tmp_stride bytes
+	 * per timing stream and one for the context stream (mosrx_time_op) */
+	uint8_t *fwd_tmp;
+	size_t fwd_tmp_stride, fwd_tmp_bytes, fwd_tmp_cap;
+	uint32_t fwd_tmp_n;
 };
 
 int mosrx__check_batch(const mosrx_batch *b, int dev);

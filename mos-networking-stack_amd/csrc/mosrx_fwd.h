@@ -1,0 +1,73 @@
+/*
+ * mosrx_fwd.h — shared between the C host library (mosrx_api.c) and the
+ * forwarding kernels (mosrx_fwd.hip).  Plain C layout.  Kept out of
+ * mosrx_internal.h, which is embedded for hipRTC: the fused kernels' source
+ * does not change with it.
+ */
+#ifndef MOSRX_FWD_H
+#define MOSRX_FWD_H
+
+#include "../../include/mosrx.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Frames per workgroup of the build's totals and copy launches: one lane per
+ * frame for the scan inside the tile, then the tile's 16-byte TX units dealt
+ * round robin over the same lanes.  One 16-byte row of scratch per tile. */
+#define MOSRX_FWD_TILE    256u
+#define MOSRX_FWD_THREADS 256u
+#define MOSRX_FWD_ROW     16u   /* scratch bytes per tile */
+
+/* The tables as the kernels read them: one device block per mosrx_fwd_set.
+ * Structure of arrays, so a wave's walk reads one address per step (an LDS
+ * broadcast once the plan kernel has copied the walked part in).  An ARP entry
+ * with prefix 1 (GetDestinationHWaddr's exact-address form, arp.c:102-106) is
+ * stored with mask ~0 and masked_ip = ip: one test serves both forms. */
+typedef struct mosrx_fwd_dev {
+	uint32_t num_routes, num_arp, num_netdevs;
+	int32_t  has_nic_fwd;
+	int8_t   nic_fwd[MOSRX_FWD_MAX_NETDEVS];
+	uint8_t  netdev_haddr[MOSRX_FWD_MAX_NETDEVS][8];   /* 6 used */
+	uint32_t r_mask[MOSRX_FWD_MAX_ROUTES], r_masked[MOSRX_FWD_MAX_ROUTES];
+	int32_t  r_prefix[MOSRX_FWD_MAX_ROUTES], r_nif[MOSRX_FWD_MAX_ROUTES];
+	uint32_t a_mask[MOSRX_FWD_MAX_ARP], a_masked[MOSRX_FWD_MAX_ARP];
+	int32_t  a_prefix[MOSRX_FWD_MAX_ARP];
+	uint8_t  a_haddr[MOSRX_FWD_MAX_ARP][8];            /* 6 used; read by the copy launch only */
+} mosrx_fwd_dev;
+
+typedef struct mosrx_fparams {
+	/* the batch and its records */
+	const uint8_t  *frames;
+	const uint32_t *off;
+	const uint16_t *len;
+	const uint8_t  *rec;         /* n records of rec_bytes, aligned to rec_bytes (plan only) */
+	const mosrx_fwd_dev *tab;
+	mosrx_fwd      *plan;        /* n, 8-byte aligned: written by the plan, read by the build */
+	uint32_t frames_bytes, n, rec_bytes;
+	int32_t  in_ifidx;           /* 0 .. MOSRX_FWD_MAX_NETDEVS - 1 */
+	int32_t  forward;            /* mosrx_mos_forwards' parameters */
+	uint32_t num_msp, listener;
+	/* the build's outputs */
+	uint32_t  cap_units;         /* tx_cap / 16 */
+	uint8_t  *tx;                /* 16-byte aligned */
+	uint32_t *tx_off;
+	uint16_t *tx_len;
+	int8_t   *tx_nif;
+	uint32_t *tx_src;
+	uint32_t *tx_count;          /* 2 */
+	uint32_t *scratch;           /* tiles rows of MOSRX_FWD_ROW bytes */
+	uint32_t  tiles;
+} mosrx_fparams;
+
+/* The plan launch, and the build's three (totals, scan, copy), on `stream` (a
+ * hipStream_t); 0, -EINVAL or -EIO.  Allocate nothing.  n == 0: the plan
+ * launches nothing, the build its scan alone (tx_count = {0, 0}). */
+int mosrx_launch_fwd_plan(const mosrx_fparams *fp, void *stream);
+int mosrx_launch_fwd_build(const mosrx_fparams *fp, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

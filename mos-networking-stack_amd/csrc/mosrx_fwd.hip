@@ -1,0 +1,453 @@
+// mosrx_fwd.hip — forwarding for forward = 1 stacks: what ProcessPacket does
+// with a frame it passes on, over a classified batch.
+//
+//   plan   one lane per frame: mosrx_mos_forwards' rule on the record's reason,
+//          then ForwardEthernetFrame (eth_out.c:104-134) or ForwardIPPacket
+//          (ip_out.c:39-110) up to the point where mOS asks for a TX buffer:
+//          the nic_forward_table entry, else GetOutputInterface's walk
+//          (ip_out.c:11-37) and GetDestinationHWaddr's (arp.c:88-119), both
+//          over tables held in LDS (every lane reads the same entry per step:
+//          a broadcast read).  One 8-byte mosrx_fwd per frame, one store.
+//   build  three ordinary launches over tiles of MOSRX_FWD_TILE frames:
+//     1. totals  per tile: 16-byte TX units and sent frames (from the plan)
+//     2. scan    one workgroup: exclusive prefix over the tiles' totals (each
+//                tile's base overwrites its row), tx_count = {0, 0}
+//     3. copy    per tile: the same per-frame units scanned inside the tile,
+//                tx_off / tx_len / tx_nif / tx_src stored, then the tile's TX
+//                units dealt round robin over the lanes -- lane-adjacent units
+//                are adjacent 16-byte stores -- each unit finding its frame by
+//                binary search of the tile's unit starts in LDS.
+// No workgroup waits on another within a launch; every loop's bound is known
+// at its entry; every store is guarded by the frame fitting tx_cap (units are
+// recomputed from the plan in the copy launch itself, so a plan that changes
+// under the launches cannot move a store out of tx_frames) and j < n.
+//
+// Sent frame j starts at 16 k + 2: its 14-byte header fills bytes 2..15 of its
+// first unit (one short + three dword stores), and unit r >= 1 holds frame
+// bytes 16 r - 2 .. 16 r + 13, read from any source alignment as five aligned
+// dwords through the batch's buffer resource and realigned with v_alignbyte;
+// one dwordx4 store, partial dwords / bytes only in a frame's last unit.
+// Padding between frames is never written.
+#include <hip/hip_runtime.h>
+#include <errno.h>
+#include <stdint.h>
+
+#include "mosrx_device.h"
+#include "mosrx_fwd.h"
+
+#define FWD_SCAN_THREADS 1024u
+#define FWD_WAVES (MOSRX_FWD_THREADS / 64u)
+
+static_assert(sizeof(mosrx_fwd) == 8 && MOSRX_FWD_ROW == 16u, "8-byte plan records, 16-byte scratch rows");
+static_assert(MOSRX_FWD_TILE == MOSRX_FWD_THREADS && MOSRX_FWD_TILE == 256u, "one lane per frame; 8 search steps");
+
+// bytes a .. a+3 of the batch buffer, any alignment (zero past its end)
+__device__ __forceinline__ uint32_t fwd_ld32(__amdgpu_buffer_rsrc_t r, uint32_t a)
+{
+	const uint32_t a4 = a & ~3u;
+	const uint32_t lo = __builtin_amdgcn_raw_buffer_load_b32(r, a4, 0, 0);
+	const uint32_t hi = __builtin_amdgcn_raw_buffer_load_b32(r, a4 + 4u, 0, 0);
+	return __builtin_amdgcn_alignbyte(hi, lo, a & 3u);
+}
+
+// bytes a .. a+15
+__device__ __forceinline__ u32x4 fwd_ld128(__amdgpu_buffer_rsrc_t r, uint32_t a)
+{
+	const uint32_t a4 = a & ~3u, sh = a & 3u;
+	const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(r, a4, 0, 0);
+	const uint32_t e = __builtin_amdgcn_raw_buffer_load_b32(r, a4 + 16u, 0, 0);
+	u32x4 v;
+	v.x = __builtin_amdgcn_alignbyte(q.y, q.x, sh);
+	v.y = __builtin_amdgcn_alignbyte(q.z, q.y, sh);
+	v.z = __builtin_amdgcn_alignbyte(q.w, q.z, sh);
+	v.w = __builtin_amdgcn_alignbyte(e, q.w, sh);
+	return v;
+}
+
+// ---- plan ------------------------------------------------------------------
+template <uint32_t RB>
+__global__ __launch_bounds__(MOSRX_FWD_THREADS) void mosrx_fwd_plan_kernel(mosrx_fparams p)
+{
+	__shared__ uint32_t s_rm[MOSRX_FWD_MAX_ROUTES], s_rv[MOSRX_FWD_MAX_ROUTES];
+	__shared__ int32_t s_rp[MOSRX_FWD_MAX_ROUTES], s_rn[MOSRX_FWD_MAX_ROUTES];
+	__shared__ uint32_t s_am[MOSRX_FWD_MAX_ARP], s_av[MOSRX_FWD_MAX_ARP];
+	__shared__ int32_t s_ap[MOSRX_FWD_MAX_ARP];
+	const mosrx_fwd_dev *T = p.tab;
+	const uint32_t t = threadIdx.x, i = blockIdx.x * MOSRX_FWD_THREADS + t;
+	const uint32_t nr = min(T->num_routes, (uint32_t)MOSRX_FWD_MAX_ROUTES);
+	const uint32_t na = min(T->num_arp, (uint32_t)MOSRX_FWD_MAX_ARP);
+	// nic_forward_table[in_ifidx], -1 without a table: uniform over the launch
+	const int32_t nicout = T->has_nic_fwd ? (int32_t)T->nic_fwd[p.in_ifidx & (MOSRX_FWD_MAX_NETDEVS - 1)] : -1;
+	const bool walk = nicout == -1;   // else ForwardIPPacket's fast path: no table is read
+	if (walk) {
+		for (uint32_t j = t; j < nr; j += MOSRX_FWD_THREADS) {
+			s_rm[j] = T->r_mask[j];
+			s_rv[j] = T->r_masked[j];
+			s_rp[j] = T->r_prefix[j];
+			s_rn[j] = T->r_nif[j];
+		}
+		for (uint32_t j = t; j < na; j += MOSRX_FWD_THREADS) {
+			s_am[j] = T->a_mask[j];
+			s_av[j] = T->a_masked[j];
+			s_ap[j] = T->a_prefix[j];
+		}
+	}
+	__syncthreads();
+	if (i >= p.n)
+		return;
+	const uint32_t reason = *reinterpret_cast<const uint32_t *>(p.rec + (uint64_t)i * RB + (RB - 4u)) & 0xFFu;
+	const uint32_t o = p.off[i];
+	const uint32_t cap = eff_caplen(o, p.len[i], p.frames_bytes);
+	const __amdgpu_buffer_rsrc_t rs = frame_rsrc(p.frames, p.frames_bytes);
+	const uint32_t w_len = fwd_ld32(rs, o + 16u);     // iph->tot_len (network order) in the low half
+	const uint32_t daddr = fwd_ld32(rs, o + 30u);     // iph->daddr as mOS loads it
+	const uint32_t ip_len = ((w_len & 0xFFu) << 8) | ((w_len >> 8) & 0xFFu);
+	// mosrx_mos_forwards (csrc/rx_loop.c)
+	const uint32_t bit = 1u << reason;
+	const uint32_t m_msp = (1u << MOSRX_R_NON_IPV4) | (1u << MOSRX_R_ARP) | (1u << MOSRX_R_NOT_TCP) |
+	                       (1u << MOSRX_R_TCP_BADCSUM);
+	const uint32_t m_tcp = (1u << MOSRX_R_TCP_OK) | (1u << MOSRX_R_TCP_LEN_OK);
+	bool fwd = false;
+	if (reason < MOSRX_R_COUNT)
+		fwd = (bit & m_msp) ? p.num_msp != 0
+		    : (bit & m_tcp) ? (p.num_msp != 0 && !p.listener)
+		    : reason == MOSRX_R_NOVERIFY_PASS;
+	fwd = fwd && p.forward;
+	const bool eth = reason == MOSRX_R_NON_IPV4 || reason == MOSRX_R_ARP;
+	// an IPv4 frame whose packet does not lie inside the capture is TRUNCATED or
+	// IP_SHORT to the classify kernels: never forwarded, whatever the record says
+	const bool ip_ok = cap >= 34u && ip_len >= 20u && 14u + ip_len <= cap;
+
+	// GetOutputInterface: from prefix -1, strictly greater wins
+	int32_t best = -1, nif = -1;
+	// GetDestinationHWaddr: from prefix 0; a prefix-1 entry matches its exact
+	// address, ends the walk and overrides what was found before it
+	int32_t abest = 0;
+	uint32_t aidx = 0xFFFFu;
+	if (walk) {
+		for (uint32_t j = 0; j < nr; j++) {
+			const int32_t pf = s_rp[j];
+			if ((daddr & s_rm[j]) == s_rv[j] && pf > best) {
+				best = pf;
+				nif = s_rn[j];
+			}
+		}
+		bool done = false;
+		for (uint32_t j = 0; j < na; j++) {
+			const int32_t pf = s_ap[j];
+			const bool m = (daddr & s_am[j]) == s_av[j];
+			const bool take = !done && m && (pf == 1 || pf > abest);
+			if (take) {
+				aidx = j;
+				abest = pf == 1 ? abest : pf;
+				done = pf == 1;
+			}
+		}
+	}
+	uint32_t kind = MOSRX_FWD_NONE, tx_len = 0, arp = 0xFFFFu;
+	int32_t oif = -1;
+	if (fwd && eth && cap >= 14u) {
+		if (nicout == -1)
+			kind = MOSRX_FWD_NO_NIC;
+		else {
+			kind = MOSRX_FWD_ETH;
+			tx_len = cap;
+			oif = nicout;
+		}
+	} else if (fwd && !eth && ip_ok) {
+		if (!walk) {
+			kind = MOSRX_FWD_IP;
+			oif = nicout;
+		} else if (nif < 0)
+			kind = MOSRX_FWD_NO_ROUTE;
+		else if (aidx == 0xFFFFu) {
+			kind = MOSRX_FWD_NO_ARP;
+			oif = nif;
+		} else {
+			kind = MOSRX_FWD_IP;
+			oif = nif;
+			arp = aidx;
+		}
+		if (kind == MOSRX_FWD_IP)
+			tx_len = 14u + ip_len;
+	}
+	u32x2 v;
+	v.x = tx_len | (((uint32_t)oif & 0xFFu) << 16) | (kind << 24);
+	v.y = arp;
+	*reinterpret_cast<u32x2 *>(p.plan + i) = v;
+}
+
+// ---- build -----------------------------------------------------------------
+// A plan record's share of the TX run: sent (kind IP or ETH with a whole
+// Ethernet header) and its 16-byte units, ceil((2 + tx_len) / 16).
+__device__ __forceinline__ uint32_t fwd_units(u32x2 pl)
+{
+	const uint32_t kind = pl.x >> 24, tx_len = pl.x & 0xFFFFu;
+	const bool sent = (kind == MOSRX_FWD_IP || kind == MOSRX_FWD_ETH) && tx_len >= 14u;
+	return sent ? (tx_len + 2u + 15u) >> 4 : 0u;
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane)
+{
+#pragma unroll
+	for (uint32_t o = 1; o < 64u; o <<= 1) {
+		const uint32_t x = __shfl_up(v, o);
+		v += lane >= o ? x : 0u;
+	}
+	return v;
+}
+
+// The tile's frames: this lane's exclusive unit offset and sent rank inside
+// the tile; tot_units / tot_sent the tile's totals (the same in every lane).
+__device__ __forceinline__ void fwd_tile_scan(uint32_t units, uint32_t *s_wu, uint32_t *s_wc, uint32_t &excl,
+                                              uint32_t &rank, uint32_t &tot_units, uint32_t &tot_sent)
+{
+	const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+	const uint32_t inc = wave_incl_scan(units, lane);
+	const uint64_t sm = __ballot(units != 0u);
+	const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+	if (lane == 63u) {
+		s_wu[wave] = inc;
+		s_wc[wave] = (uint32_t)__builtin_popcountll(sm);
+	}
+	__syncthreads();
+	uint32_t bu = 0, bc = 0;
+	tot_units = tot_sent = 0;
+#pragma unroll
+	for (uint32_t w = 0; w < FWD_WAVES; w++) {
+		const uint32_t u = s_wu[w], c = s_wc[w];
+		bu += w < wave ? u : 0u;
+		bc += w < wave ? c : 0u;
+		tot_units += u;
+		tot_sent += c;
+	}
+	excl = bu + inc - units;
+	rank = bc + below;
+}
+
+// 1. totals: scratch row = {units, sent, 0, 0}
+__global__ __launch_bounds__(MOSRX_FWD_THREADS) void mosrx_fwd_totals_kernel(mosrx_fparams p)
+{
+	__shared__ uint32_t s_wu[FWD_WAVES], s_wc[FWD_WAVES];
+	if (blockIdx.x >= p.tiles)
+		return;
+	const uint32_t t = threadIdx.x, i = blockIdx.x * MOSRX_FWD_TILE + t;
+	u32x2 pl = {0u, 0u};
+	if (i < p.n)
+		pl = *reinterpret_cast<const u32x2 *>(p.plan + i);
+	uint32_t excl, rank, tu, ts;
+	fwd_tile_scan(fwd_units(pl), s_wu, s_wc, excl, rank, tu, ts);
+	if (t == 0) {
+		u32x4 row = {tu, ts, 0u, 0u};
+		*reinterpret_cast<u32x4 *>(p.scratch + 4u * blockIdx.x) = row;
+	}
+}
+
+// 2. scan: lane t owns a run of `per` consecutive tiles; rows become
+//    {unit base lo, unit base hi, sent base, 0}
+__global__ __launch_bounds__(FWD_SCAN_THREADS) void mosrx_fwd_scan_kernel(mosrx_fparams p)
+{
+	__shared__ uint64_t s_u[FWD_SCAN_THREADS];
+	__shared__ uint32_t s_c[FWD_SCAN_THREADS];
+	const uint32_t t = threadIdx.x;
+	if (blockIdx.x != 0)
+		return;
+	const uint32_t per = (p.tiles + FWD_SCAN_THREADS - 1u) / FWD_SCAN_THREADS;
+	const uint32_t t0 = min(t * per, p.tiles), t1 = min(t0 + per, p.tiles);
+	uint64_t su = 0;
+	uint32_t sc = 0;
+	for (uint32_t r = t0; r < t1; r++) {
+		su += p.scratch[4u * r];
+		sc += p.scratch[4u * r + 1u];
+	}
+	s_u[t] = su;
+	s_c[t] = sc;
+	__syncthreads();
+	// inclusive prefix over the 1024 runs (Hillis-Steele, 10 steps)
+#pragma unroll
+	for (uint32_t o = 1; o < FWD_SCAN_THREADS; o <<= 1) {
+		const uint64_t vu = t >= o ? s_u[t - o] : 0u;
+		const uint32_t vc = t >= o ? s_c[t - o] : 0u;
+		__syncthreads();
+		s_u[t] += vu;
+		s_c[t] += vc;
+		__syncthreads();
+	}
+	uint64_t ru = s_u[t] - su;
+	uint32_t rc = s_c[t] - sc;
+	for (uint32_t r = t0; r < t1; r++) {
+		const uint32_t u = p.scratch[4u * r], c = p.scratch[4u * r + 1u];
+		u32x4 row = {(uint32_t)ru, (uint32_t)(ru >> 32), rc, 0u};
+		*reinterpret_cast<u32x4 *>(p.scratch + 4u * r) = row;
+		ru += u;
+		rc += c;
+	}
+	if (t == 0) {
+		p.tx_count[0] = 0;
+		p.tx_count[1] = 0;
+	}
+}
+
+// 3. copy
+__global__ __launch_bounds__(MOSRX_FWD_THREADS) void mosrx_fwd_copy_kernel(mosrx_fparams p)
+{
+	__shared__ uint32_t s_wu[FWD_WAVES], s_wc[FWD_WAVES];
+	__shared__ uint32_t s_start[MOSRX_FWD_TILE + 1u];   // unit start of the tile's k-th sent frame; [sent]: the tile's units
+	__shared__ uint32_t s_off[MOSRX_FWD_TILE];          // its source offset
+	__shared__ uint32_t s_meta[MOSRX_FWD_TILE];         // its plan word 0 (tx_len, out_ifidx, kind); 0: does not fit
+	__shared__ uint32_t s_arp[MOSRX_FWD_TILE];
+	if (blockIdx.x >= p.tiles)
+		return;
+	const uint32_t t = threadIdx.x, i = blockIdx.x * MOSRX_FWD_TILE + t;
+	u32x2 pl = {0u, 0u};
+	uint32_t o = 0;
+	if (i < p.n) {
+		pl = *reinterpret_cast<const u32x2 *>(p.plan + i);
+		o = p.off[i];
+	}
+	const u32x4 row = *reinterpret_cast<const u32x4 *>(p.scratch + 4u * blockIdx.x);
+	const uint64_t ubase = (uint64_t)row.x | ((uint64_t)row.y << 32);
+	const uint32_t units = fwd_units(pl);
+	uint32_t excl, rank, tu, ts;
+	fwd_tile_scan(units, s_wu, s_wc, excl, rank, tu, ts);
+	const bool sent = units != 0u;
+	const uint64_t k = ubase + excl;
+	const bool fits = sent && k + units <= (uint64_t)p.cap_units;
+	const uint32_t j = row.z + rank;
+	if (sent) {
+		s_start[rank] = excl;
+		s_off[rank] = o;
+		s_meta[rank] = fits ? pl.x : 0u;
+		s_arp[rank] = pl.y & 0xFFFFu;
+	}
+	if (t == 0)
+		s_start[ts] = tu;
+	if (fits && j < p.n) {
+		p.tx_off[j] = (uint32_t)(k * 16u + 2u);
+		p.tx_len[j] = (uint16_t)(pl.x & 0xFFFFu);
+		p.tx_nif[j] = (int8_t)((pl.x >> 16) & 0xFFu);
+		p.tx_src[j] = i;
+	}
+	{
+		const uint32_t nfit = (uint32_t)__builtin_popcountll(__ballot(fits && j < p.n));
+		const uint32_t ndrop = (uint32_t)__builtin_popcountll(__ballot(sent && !(fits && j < p.n)));
+		if ((t & 63u) == 0u) {
+			if (nfit)
+				atomicAdd(&p.tx_count[0], nfit);
+			if (ndrop)
+				atomicAdd(&p.tx_count[1], ndrop);
+		}
+	}
+	__syncthreads();
+	const __amdgpu_buffer_rsrc_t rs = frame_rsrc(p.frames, p.frames_bytes);
+	const mosrx_fwd_dev *T = p.tab;
+	for (uint32_t u = t; u < tu; u += MOSRX_FWD_THREADS) {
+		// the sent frame that holds unit u: the last one starting at or before it
+		uint32_t lo = 0, hi = ts;
+#pragma unroll
+		for (int it = 0; it < 8; it++) {
+			const uint32_t mid = (lo + hi) >> 1;
+			const bool go = hi - lo > 1u;
+			const bool le = s_start[mid] <= u;
+			lo = go && le ? mid : lo;
+			hi = go && !le ? mid : hi;
+		}
+		const uint32_t meta = s_meta[lo];
+		if (!meta)
+			continue;                      // the frame does not fit tx_cap
+		const uint32_t r = u - s_start[lo];
+		const uint32_t tx_len = meta & 0xFFFFu;
+		const uint64_t ku = ubase + u;
+		if (ku >= (uint64_t)p.cap_units)
+			continue;                      // (holds by construction: the frame's last unit fits)
+		uint8_t *dst = p.tx + ku * 16u;
+		if (r == 0) {
+			// the Ethernet header: EthernetOutput's rewrite for an IP frame, a copy otherwise
+			u32x4 h = fwd_ld128(rs, s_off[lo]);
+			if ((meta >> 24) == MOSRX_FWD_IP) {
+				const uint32_t ai = s_arp[lo];
+				const uint32_t nif = (meta >> 16) & (MOSRX_FWD_MAX_NETDEVS - 1u);
+				const uint32_t *sm = reinterpret_cast<const uint32_t *>(T->netdev_haddr[nif]);
+				const uint32_t s0 = sm[0], s1 = sm[1] & 0xFFFFu;
+				uint32_t d0 = h.x, d1 = h.y & 0xFFFFu;   // the frame's own h_dest (nic_forward_table path)
+				if (ai < MOSRX_FWD_MAX_ARP) {
+					const uint32_t *dm = reinterpret_cast<const uint32_t *>(T->a_haddr[ai]);
+					d0 = dm[0];
+					d1 = dm[1] & 0xFFFFu;
+				}
+				h.x = d0;
+				h.y = d1 | (s0 << 16);
+				h.z = (s0 >> 16) | (s1 << 16);
+			}
+			*reinterpret_cast<uint16_t *>(dst + 2) = (uint16_t)h.x;
+			*reinterpret_cast<uint32_t *>(dst + 4) = (h.x >> 16) | (h.y << 16);
+			*reinterpret_cast<uint32_t *>(dst + 8) = (h.y >> 16) | (h.z << 16);
+			*reinterpret_cast<uint32_t *>(dst + 12) = (h.z >> 16) | (h.w << 16);
+		} else {
+			const uint32_t b0 = 16u * r - 2u;      // the unit's first frame byte; < tx_len
+			const uint32_t rem = tx_len - b0;
+			const u32x4 v = fwd_ld128(rs, s_off[lo] + b0);
+			if (rem >= 16u) {
+				*reinterpret_cast<u32x4 *>(dst) = v;
+			} else {
+				const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+				const uint32_t nd = rem >> 2;
+				uint32_t last = 0;
+#pragma unroll
+				for (uint32_t q = 0; q < 4u; q++) {
+					if (q < nd)
+						reinterpret_cast<uint32_t *>(dst)[q] = w[q];
+					last = q == nd ? w[q] : last;
+				}
+				uint8_t *e = dst + 4u * nd;
+				if (rem & 2u) {
+					*reinterpret_cast<uint16_t *>(e) = (uint16_t)last;
+					e += 2;
+					last >>= 16;
+				}
+				if (rem & 1u)
+					*e = (uint8_t)last;
+			}
+		}
+	}
+}
+
+static int fwd_common_ok(const mosrx_fparams *fp)
+{
+	return fp && fp->tab && fp->plan && !((uintptr_t)fp->plan & 7) &&
+	       (fp->n == 0 || (fp->frames && fp->off && fp->len && !((uintptr_t)fp->off & 3) && !((uintptr_t)fp->len & 1)));
+}
+
+extern "C" int mosrx_launch_fwd_plan(const mosrx_fparams *fp, void *stream)
+{
+	const hipStream_t s = (hipStream_t)stream;
+	if (!fwd_common_ok(fp) || (fp->rec_bytes != 8u && fp->rec_bytes != 16u) || fp->in_ifidx < 0 ||
+	    fp->in_ifidx >= MOSRX_FWD_MAX_NETDEVS)
+		return -EINVAL;
+	if (fp->n == 0)
+		return 0;
+	if (!fp->rec || ((uintptr_t)fp->rec & (fp->rec_bytes - 1u)))
+		return -EINVAL;
+	const dim3 grid((fp->n + MOSRX_FWD_THREADS - 1u) / MOSRX_FWD_THREADS), block(MOSRX_FWD_THREADS);
+	if (fp->rec_bytes == 8u)
+		hipLaunchKernelGGL(mosrx_fwd_plan_kernel<8u>, grid, block, 0, s, *fp);
+	else
+		hipLaunchKernelGGL(mosrx_fwd_plan_kernel<16u>, grid, block, 0, s, *fp);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+extern "C" int mosrx_launch_fwd_build(const mosrx_fparams *fp, void *stream)
+{
+	const hipStream_t s = (hipStream_t)stream;
+	if (!fwd_common_ok(fp) || !fp->tx || ((uintptr_t)fp->tx & 15) || !fp->tx_off || ((uintptr_t)fp->tx_off & 3) ||
+	    !fp->tx_len || ((uintptr_t)fp->tx_len & 1) || !fp->tx_nif || !fp->tx_src || ((uintptr_t)fp->tx_src & 3) ||
+	    !fp->tx_count || ((uintptr_t)fp->tx_count & 3) || !fp->scratch || ((uintptr_t)fp->scratch & 15) ||
+	    fp->tiles != (fp->n + MOSRX_FWD_TILE - 1u) / MOSRX_FWD_TILE)
+		return -EINVAL;
+	if (fp->tiles)
+		hipLaunchKernelGGL(mosrx_fwd_totals_kernel, dim3(fp->tiles), dim3(MOSRX_FWD_THREADS), 0, s, *fp);
+	hipLaunchKernelGGL(mosrx_fwd_scan_kernel, dim3(1), dim3(FWD_SCAN_THREADS), 0, s, *fp);
+	if (fp->tiles)
+		hipLaunchKernelGGL(mosrx_fwd_copy_kernel, dim3(fp->tiles), dim3(MOSRX_FWD_THREADS), 0, s, *fp);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}

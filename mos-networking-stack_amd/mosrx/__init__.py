@@ -115,6 +115,81 @@ TX_CHECK_DTYPE = np.dtype([("ip_check", "<u2"), ("tcp_check", "<u2"), ("what", "
                            ("pad", "<u2")])
 BPF_MAX_PROGS = 32
 
+# ---- forwarding (include/mosrx.h: mosrx_fwd_tables, mosrx_fwd) ----
+OP_FWD_PLAN = 10       # MOSRX_OP_FWD_PLAN: the forwarding plan (arg = rec_bytes | in_ifidx << 8)
+OP_FWD = 11            # MOSRX_OP_FWD: plan + build
+FWD_MAX_ROUTES, FWD_MAX_ARP, FWD_MAX_NETDEVS = 128, 1024, 16
+FWD_NONE, FWD_IP, FWD_ETH, FWD_NO_ROUTE, FWD_NO_ARP, FWD_NO_NIC = range(6)   # MOSRX_FWD_*
+# mosrx_fwd: the plan of one frame
+FWD_DTYPE = np.dtype([("tx_len", "<u2"), ("out_ifidx", "i1"), ("kind", "u1"), ("arp_idx", "<u2"),
+                      ("reserved", "<u2")])
+assert FWD_DTYPE.itemsize == 8
+
+
+class FwdRoute(C.Structure):
+    _fields_ = [("mask", C.c_uint32), ("masked_ip", C.c_uint32), ("prefix", C.c_int32), ("nif", C.c_int32)]
+
+
+class FwdArp(C.Structure):
+    _fields_ = [("ip", C.c_uint32), ("mask", C.c_uint32), ("masked_ip", C.c_uint32), ("prefix", C.c_int32),
+                ("haddr", C.c_uint8 * 6), ("pad", C.c_uint8 * 2)]
+
+
+class FwdTables(C.Structure):
+    """mosrx_fwd_tables: the route / ARP / netdev / nic_forward fields mOS holds after mos.conf."""
+    _fields_ = [("num_routes", C.c_uint32), ("num_arp", C.c_uint32), ("num_netdevs", C.c_uint32),
+                ("has_nic_fwd", C.c_int32), ("nic_fwd", C.c_int8 * FWD_MAX_NETDEVS),
+                ("netdev_haddr", (C.c_uint8 * 6) * FWD_MAX_NETDEVS), ("routes", FwdRoute * FWD_MAX_ROUTES),
+                ("arp", FwdArp * FWD_MAX_ARP)]
+
+
+def conf_mask(prefix: int) -> int:
+    """htonl((prefix == 0) ? 0 : ((-1) << (32 - prefix))) as config.c:316, :346 store it
+    (network order, the raw u32 of a little-endian host)."""
+    host = 0 if prefix == 0 else (0xFFFFFFFF << (32 - prefix)) & 0xFFFFFFFF
+    return int.from_bytes(host.to_bytes(4, "big"), "little")
+
+
+def mac_bytes(m: str) -> bytes:
+    b = bytes(int(x, 16) for x in m.split(":"))
+    assert len(b) == 6, m
+    return b
+
+
+def fwd_tables(routes=(), arp=(), netdevs=(), nic_fwd=None) -> FwdTables:
+    """The tables of a mos.conf: routes [("10.0.0.0/8", nif)], arp [("10.1.0.0/16",
+    "02:00:00:00:00:01")], netdevs ["02:..", ...] (each netdev's haddr), nic_fwd
+    None (no nic_forward_table) or {in_ifidx: out_ifidx} (the others -1).  mask
+    and masked_ip exactly as FeedArpConfLine / FeedRouteConfLine compute them
+    (config.c:314-317, 345-348); prefixes 0..32."""
+    t = FwdTables()
+    assert len(routes) <= FWD_MAX_ROUTES and len(arp) <= FWD_MAX_ARP and len(netdevs) <= FWD_MAX_NETDEVS
+    t.num_routes, t.num_arp, t.num_netdevs = len(routes), len(arp), len(netdevs)
+    for i, m in enumerate(netdevs):
+        t.netdev_haddr[i][:] = list(mac_bytes(m))
+    for i, (cidr, nif) in enumerate(routes):
+        a, p = cidr.split("/")
+        p = int(p)
+        assert 0 <= p <= 32, cidr
+        r = t.routes[i]
+        r.mask = conf_mask(p)
+        r.masked_ip = r.mask & ip_raw(a)
+        r.prefix, r.nif = p, int(nif)
+    for i, (cidr, mac) in enumerate(arp):
+        a, p = cidr.split("/")
+        p = int(p)
+        assert 0 <= p <= 32, cidr
+        e = t.arp[i]
+        e.ip = ip_raw(a)
+        e.prefix = p
+        e.mask = conf_mask(p)
+        e.masked_ip = e.mask & e.ip
+        e.haddr[:] = list(mac_bytes(mac))
+    t.has_nic_fwd = 0 if nic_fwd is None else 1
+    for i in range(FWD_MAX_NETDEVS):
+        t.nic_fwd[i] = -1 if nic_fwd is None else int(dict(nic_fwd).get(i, -1))
+    return t
+
 
 class BpfProg(C.Structure):
     _fields_ = [("insns", C.c_void_p), ("len", C.c_uint32), ("len_mode", C.c_int32)]
@@ -388,6 +463,12 @@ def lib():
             "mosrx_gpu_module_steer_one_count": (U64, [P]),
             "mosrx_gpu_module_set_steer_one": (I, [C.c_int32]),
             "mosrx_gpu_module_get_steer_one": (C.c_int32, []),
+            "mosrx_fwd_set": (I, [P, C.POINTER(FwdTables)]),
+            "mosrx_fwd_set_listener": (I, [P, I]),
+            "mosrx_fwd_plan_dev": (I, [P, C.POINTER(Batch), P, I, I, P, P]),
+            "mosrx_fwd_build_dev": (I, [P, C.POINTER(Batch), P, P, U64, P, P, P, P, P, P, C.c_size_t, P]),
+            "mosrx_fwd_scratch_bytes": (C.c_size_t, [U32]),
+            "mosrx_fwd_tile": (U32, []),
             "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
             "mosrx_hub_endpoint": (P, [P, U32]),
             "mosrx_hub_stats_get": (I, [P, P]),
@@ -579,6 +660,7 @@ class DevBatch:
         self.d_match = None   # allocated on the first bpf_dev
         self.d_out8 = None    # compact records, allocated on the first classify_dev_compact
         self.d_sidx = None    # steered frame indices, allocated on the first time_op(OP_STEER)
+        self.d_fplan = None   # forwarding plan records, allocated on the first time_op(OP_FWD_PLAN / OP_FWD)
         self.max_len = int(max_len if max_len is not None else (int(ln.max()) if self.n else 0))
         self.caplen_sum = int(ln.astype(np.uint64).sum())
 
@@ -623,7 +705,7 @@ class DevBatch:
 
     def free(self):
         for b in (self.d_frames, self.d_off, self.d_len, self.d_out, self.d_fhash, self.d_match, self.d_tinfo,
-                  self.d_out8, self.d_sidx):
+                  self.d_out8, self.d_sidx, self.d_fplan):
             if b is not None:
                 b.free()
 
@@ -884,6 +966,33 @@ class Context:
         if sync:
             _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
 
+    # ---- forwarding ----
+    def fwd_set(self, tables: FwdTables | None) -> None:
+        """mosrx_fwd_set: install the forwarding tables (None clears them)."""
+        _chk(lib().mosrx_fwd_set(self.handle, C.byref(tables) if tables is not None else None), "mosrx_fwd_set")
+
+    def fwd_set_listener(self, listener: bool) -> None:
+        _chk(lib().mosrx_fwd_set_listener(self.handle, int(bool(listener))), "mosrx_fwd_set_listener")
+
+    def fwd_plan_dev(self, b: Batch, d_rec: int, rec_bytes: int, in_ifidx: int, d_plan: int, sync: bool = True,
+                     stream: int | None = None) -> None:
+        """mosrx_fwd_plan_dev: one mosrx_fwd (FWD_DTYPE) per frame of a device-resident
+        batch from its records (device pointers; the caller owns all)."""
+        _chk(lib().mosrx_fwd_plan_dev(self.handle, C.byref(b), d_rec, rec_bytes, in_ifidx, d_plan, stream),
+             "mosrx_fwd_plan_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
+    def fwd_build_dev(self, b: Batch, d_plan: int, d_tx_frames: int, tx_cap: int, d_tx_off: int, d_tx_len: int,
+                      d_tx_nif: int, d_tx_src: int, d_tx_count: int, d_scratch: int, scratch_bytes: int,
+                      sync: bool = True, stream: int | None = None) -> None:
+        """mosrx_fwd_build_dev: the TX frames of a planned batch, in arrival order."""
+        _chk(lib().mosrx_fwd_build_dev(self.handle, C.byref(b), d_plan, d_tx_frames, tx_cap, d_tx_off, d_tx_len,
+                                       d_tx_nif, d_tx_src, d_tx_count, d_scratch, scratch_bytes, stream),
+             "mosrx_fwd_build_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
     def slot_steer(self, slot: int, idx: list | None, qstart: list | None) -> None:
         """mosrx_slot_steer: arm the slot's next group submit (host pointers per
         batch: n indices, STEER_QSLOTS queue starts); None, None disarms."""
@@ -1005,14 +1114,18 @@ class Context:
                 d.d_match = DevBuffer(self, max(d.n * 4, 4))
             if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) and d.d_sidx is None:
                 d.d_sidx = DevBuffer(self, max(d.n * 4, 4))
+            if op in (OP_FWD_PLAN, OP_FWD) and d.d_fplan is None:
+                d.d_fplan = DevBuffer(self, max(d.n * 8, 8))
         bs = (Batch * len(dbs))(*[d.batch() for d in dbs])
         # OP_STEER reads the records a classify call left: the compact ones for arg == 8
         outs = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_BPF else
-                                          d.d_out8.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) and (arg & 0xFF) == 8
+                                          d.d_out8.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE,
+                                                                 OP_FWD_PLAN, OP_FWD) and (arg & 0xFF) == 8
                                           else d.d_out.ptr) for d in dbs])
         aux = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_CLASSIFY_BPF else
                                          d.d_tinfo.ptr if op == OP_CLASSIFY_TI else
                                          d.d_sidx.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) else
+                                         d.d_fplan.ptr if op in (OP_FWD_PLAN, OP_FWD) else
                                          (d.d_fhash.ptr if d.d_fhash else None)) for d in dbs])
         tot, avg = C.c_float(), C.c_float()
         _chk(lib().mosrx_time_op(self.handle, op, arg, bs, len(dbs), outs, aux, iters, nstreams,
