@@ -468,6 +468,43 @@ int  mosrx_fwd_build_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_
 size_t   mosrx_fwd_scratch_bytes(uint32_t n);
 uint32_t mosrx_fwd_tile(void);
 
+/* The ring form of the build: the same frames, byte for byte, each in the TX
+ * ring of its output netdev, as a NIC's TX queues would hold them (mOS sends
+ * per netdev: get_wptr(ctx, nif, len) / send_pkts(ctx, nif)).  A frame is sent
+ * when its kind is IP or ETH, tx_len >= 14 and out_ifidx is in 0 .. nrings - 1.
+ *   ring q      d_tx_frames[q * ring_cap .. (q + 1) * ring_cap)
+ *   its r-th sent frame, in arrival order, at q * ring_cap + 16 k + 2, k the
+ *               exclusive scan of ceil((2 + tx_len) / 16) over netdev q's sent
+ *               frames alone
+ *   its entry   j = rings[q].start + r: tx_off[j] (from d_tx_frames), tx_len[j],
+ *               tx_src[j] (the frame's index in the batch); the ring says the netdev
+ * A frame whose padded end passes ring_cap is not written and counted in
+ * rings[q].dropped, and so is every later frame of that netdev; other netdevs
+ * are not affected.  Ring q's written frames are entries start .. start + count;
+ * entries start + count .. start + count + dropped are left untouched, as are
+ * padding, ring bytes past 16 * units, entries past the last ring and
+ * d_rings[nrings ..].  d_rings[0 .. nrings) is written whole by every call
+ * (n == 0 included); the three entry arrays need room for n entries.  Three
+ * launches on one stream; allocates nothing, graph-capturable.
+ * -EINVAL: NULL or misaligned pointer (d_tx_frames, d_rings, d_scratch to 16
+ * bytes, d_tx_off / d_tx_src to 4, d_tx_len to 2), nrings outside
+ * 1 .. MOSRX_FWD_MAX_NETDEVS or below the installed tables' num_netdevs,
+ * ring_cap not a multiple of 16 or nrings * ring_cap > 2^32 (tx_off is 32
+ * bits), scratch under mosrx_fwd_rings_scratch_bytes(n, nrings); -ENOENT: no
+ * tables set. */
+typedef struct mosrx_fwd_ring {   /* 16 bytes, one per output netdev */
+	uint32_t start;     /* first entry of this netdev in tx_off / tx_len / tx_src */
+	uint32_t count;     /* frames written to the ring */
+	uint32_t dropped;   /* sent frames of this netdev that did not fit */
+	uint32_t units;     /* 16-byte units the written frames take: the ring is filled to 16 * units */
+} mosrx_fwd_ring;
+int    mosrx_fwd_build_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan,
+                                 uint8_t *d_tx_frames, uint64_t ring_cap, uint32_t nrings,
+                                 uint32_t *d_tx_off, uint16_t *d_tx_len, uint32_t *d_tx_src,
+                                 mosrx_fwd_ring *d_rings, void *d_scratch, size_t scratch_bytes, void *stream);
+/* Scratch a ring build needs (no GPU needed; never 0, non-decreasing in both). */
+size_t mosrx_fwd_rings_scratch_bytes(uint32_t n, uint32_t nrings);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned
@@ -635,7 +672,10 @@ enum { MOSRX_OP_CLASSIFY = 0, MOSRX_OP_CLASSIFY_FH = 1, MOSRX_OP_BPF = 2, MOSRX_
                                * its mosrx_fwd plan array, `arg` = rec_bytes | in_ifidx << 8 */,
        MOSRX_OP_FWD = 11 /* MOSRX_OP_FWD_PLAN followed by the build (four launches: -ENOTSUP from
                           * mosrx_time_op_dispatch); the TX outputs and scratch are the timing call's own, tx_cap
-                          * what the batch's frames need at most */ };
+                          * what the batch's frames need at most */,
+       MOSRX_OP_FWD_RINGS = 12 /* MOSRX_OP_FWD_PLAN followed by the ring build (-ENOTSUP from
+                                * mosrx_time_op_dispatch); outputs and scratch are the timing call's own, ring_cap
+                                * what the batch's frames need at most, nrings the tables' num_netdevs */ };
 int  mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t nb, void *const *out,
                    void *const *aux, uint32_t iters, uint32_t nstreams, float *total_ms, float *avg_kernel_ms);
 /* The kernel's own duration, averaged over `iters` back-to-back launches on

@@ -516,6 +516,21 @@ int  mosrx_mos_forwards(const mosrx_result *res, int forward, uint32_t num_msp, 
 void mosrx_forward_frame(void *arg, int ifidx, int index, const uint8_t *pkt, uint16_t len,
                          const mosrx_result *res);
 
+/* Hand the TX rings of mosrx_fwd_build_rings_dev, over host copies of its
+ * outputs, to an I/O module the way mOS transmits (csrc/fwd_tx.c; no GPU in
+ * it): for each ring q in netdev order with count > 0, and each of its entries
+ * start .. start + count in order, get_wptr(ctx, q, len) and a memcpy of the
+ * frame -- a NULL return counts no_buffer and goes on, EthernetOutput failing
+ * for that frame -- then one send_pkts(ctx, q) (RunMainLoop's per-netdev flush,
+ * core.c:999-1007); a ring without frames gets no call.  Nothing outside
+ * start .. start + count of a ring's entries is read.  Returns the frames sent,
+ * or -EINVAL (a NULL argument, get_wptr or send_pkts; nrings outside
+ * 1 .. MOSRX_FWD_MAX_NETDEVS).  `st`, when given, is added to. */
+typedef struct mosrx_fwd_send_stats { uint64_t sent, no_buffer, send_calls; } mosrx_fwd_send_stats;
+int mosrx_fwd_rings_send(const io_module_func *iom, struct mtcp_thread_context *ctx,
+                         const uint8_t *h_tx_frames, const uint32_t *h_tx_off, const uint16_t *h_tx_len,
+                         const mosrx_fwd_ring *h_rings, uint32_t nrings, mosrx_fwd_send_stats *st);
+
 /* ---- residency of frames from a paced source (latency of the drop-in path) ----
  * mosrx_source_paced: `inner`'s frames released at `rate_pps` -- frame k
  * arrives at t0 + k * 1e9 / rate_pps, t0 being the first receive call -- and

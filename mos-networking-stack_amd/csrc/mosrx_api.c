@@ -1831,25 +1831,30 @@ static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
 	return 0;
 }
 
-/* MOSRX_OP_FWD's TX outputs + scratch: one block for the context stream and
- * one per timing stream, sized for the largest batch (each part rounded to
- * 256 bytes): tx_frames with room for every frame of the batch sent whole
- * (its frame bytes + 32 a frame), tx_off, tx_src, tx_len, tx_nif, tx_count,
- * scratch. */
-#define OP_IS_FWD(op) ((op) == MOSRX_OP_FWD_PLAN || (op) == MOSRX_OP_FWD)
-static int fwd_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
+/* MOSRX_OP_FWD's / MOSRX_OP_FWD_RINGS' TX outputs + scratch: one block for the
+ * context stream and one per timing stream, sized for the largest batch (each
+ * part rounded to 256 bytes): tx_frames as `nrings` rings (MOSRX_OP_FWD: one),
+ * each with room for every frame of the batch sent whole (its frame bytes + 32
+ * a frame; the rings together at most 4 GiB), tx_off, tx_src, tx_len, tx_nif,
+ * tx_count / the ring rows, scratch. */
+#define OP_IS_FWD(op) ((op) == MOSRX_OP_FWD_PLAN || (op) == MOSRX_OP_FWD || (op) == MOSRX_OP_FWD_RINGS)
+static int fwd_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, uint32_t nrings)
 {
 	uint32_t i, maxn = 0;
-	uint64_t maxb = 0;
+	uint64_t maxb = 0, cap;
 	size_t stride, bytes;
 	for (i = 0; i < nb; i++) {
 		maxn = b[i].n > maxn ? b[i].n : maxn;
 		maxb = b[i].frames_bytes > maxb ? b[i].frames_bytes : maxb;
 	}
+	cap = STEER_TMP_RND(maxb + 32ull * maxn);
+	if (nrings > 1 && cap > ((1ull << 32) / nrings & ~255ull))
+		cap = (1ull << 32) / nrings & ~255ull;
 	c->fwd_tmp_n = maxn;
-	c->fwd_tmp_cap = STEER_TMP_RND(maxb + 32ull * maxn);
-	stride = c->fwd_tmp_cap + 2 * STEER_TMP_RND((size_t)maxn * 4) + STEER_TMP_RND((size_t)maxn * 2) +
-	         STEER_TMP_RND(maxn) + 256 + STEER_TMP_RND(mosrx_fwd_scratch_bytes(maxn));
+	c->fwd_tmp_cap = cap;
+	c->fwd_tmp_rings = nrings;
+	stride = c->fwd_tmp_cap * nrings + 2 * STEER_TMP_RND((size_t)maxn * 4) + STEER_TMP_RND((size_t)maxn * 2) +
+	         STEER_TMP_RND(maxn) + 256 + STEER_TMP_RND(mosrx_fwd_rings_scratch_bytes(maxn, nrings));
 	bytes = stride * (MOSRX_MAX_STREAMS + 1);
 	if (bytes > c->fwd_tmp_bytes) {
 		HIPCHK(hipDeviceSynchronize());
@@ -1918,7 +1923,8 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 		                              (uint32_t *)qoff, (uint16_t *)qlen, blk + STEER_TMP_QS, c->steer_tmp_scratch, s);
 	}
 	case MOSRX_OP_FWD_PLAN:
-	case MOSRX_OP_FWD: {
+	case MOSRX_OP_FWD:
+	case MOSRX_OP_FWD_RINGS: {
 		uint32_t k = 0;
 		uint8_t *blk, *toff, *tsrc, *tlen, *tnif, *tcnt, *scr;
 		const size_t w = STEER_TMP_RND((size_t)c->fwd_tmp_n * 4);
@@ -1928,12 +1934,17 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 		while (k < c->nxs && c->xs[k] != s)
 			k++;
 		blk = c->fwd_tmp + (size_t)(k < c->nxs ? k + 1 : 0) * c->fwd_tmp_stride;
-		toff = blk + c->fwd_tmp_cap;
+		toff = blk + c->fwd_tmp_cap * c->fwd_tmp_rings;
 		tsrc = toff + w;
 		tlen = tsrc + w;
 		tnif = tlen + STEER_TMP_RND((size_t)c->fwd_tmp_n * 2);
 		tcnt = tnif + STEER_TMP_RND(c->fwd_tmp_n);
 		scr = tcnt + 256;
+		if (op == MOSRX_OP_FWD_RINGS)
+			return mosrx_fwd_build_rings_dev(c, b, (const mosrx_fwd *)aux, blk, c->fwd_tmp_cap, c->fwd_tmp_rings,
+			                                 (uint32_t *)toff, (uint16_t *)tlen, (uint32_t *)tsrc, (mosrx_fwd_ring *)tcnt,
+			                                 scr, STEER_TMP_RND(mosrx_fwd_rings_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)),
+			                                 s);
 		return mosrx_fwd_build_dev(c, b, (const mosrx_fwd *)aux, blk, c->fwd_tmp_cap, (uint32_t *)toff, (uint16_t *)tlen,
 		                           (int8_t *)tnif, (uint32_t *)tsrc, (uint32_t *)tcnt, scr,
 		                           STEER_TMP_RND(mosrx_fwd_scratch_bytes(c->fwd_tmp_n)), s);
@@ -2024,7 +2035,7 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 {
 	int rc;
 	if (!c || !b || nb == 0 || iters == 0 || nstreams == 0 || nstreams > MOSRX_MAX_STREAMS ||
-	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD || (op != MOSRX_OP_TX_CSUM && !out) ||
+	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_RINGS || (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
 	      OP_IS_FWD(op)) && !aux) ||
 	    (OP_IS_FWD(op) && (((arg & 0xFF) != 8 && (arg & 0xFF) != 16) || (arg >> 8) < 0 ||
@@ -2035,8 +2046,14 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 	HIPCHK(hipSetDevice(c->device));
 	if (OP_IS_STEER(op) && (rc = steer_tmp_reserve(c, b, nb)))
 		return rc;
-	if (op == MOSRX_OP_FWD && (rc = fwd_tmp_reserve(c, b, nb)))
+	if (op == MOSRX_OP_FWD && (rc = fwd_tmp_reserve(c, b, nb, 1)))
 		return rc;
+	if (op == MOSRX_OP_FWD_RINGS) {
+		if (!c->d_fwd)
+			return -ENOENT;
+		if ((rc = fwd_tmp_reserve(c, b, nb, c->fwd_num_netdevs ? c->fwd_num_netdevs : 1)))
+			return rc;
+	}
 	if (total_ms && (rc = time_streams(c, op, arg, b, nb, out, aux, iters, nstreams, total_ms)))
 		return rc;
 	if (avg_kernel_ms && (rc = time_kernels(c, op, arg, b, nb, out, aux, iters, avg_kernel_ms)))
@@ -2099,7 +2116,7 @@ int mosrx_time_op_dispatch(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, 
                            void *const *aux, uint32_t iters, float *avg_ms)
 {
 	struct op_run r = {op, arg, b, nb, out, aux};
-	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD ||
+	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_RINGS ||
 	    (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
 	      OP_IS_FWD(op)) && !aux))
@@ -2701,6 +2718,15 @@ size_t mosrx_fwd_scratch_bytes(uint32_t n)
 
 uint32_t mosrx_fwd_tile(void) { return MOSRX_FWD_TILE; }
 
+/* one row per tile and ring; nrings outside 1 .. MOSRX_FWD_MAX_NETDEVS is
+ * clamped, so the size is defined (and monotone) for every argument */
+size_t mosrx_fwd_rings_scratch_bytes(uint32_t n, uint32_t nrings)
+{
+	const size_t tiles = ((size_t)n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+	const size_t q = nrings < 1 ? 1 : nrings > MOSRX_FWD_MAX_NETDEVS ? MOSRX_FWD_MAX_NETDEVS : nrings;
+	return (tiles ? tiles : 1) * q * MOSRX_FWD_ROW;
+}
+
 int mosrx_fwd_set_listener(mosrx_ctx *c, int listener)
 {
 	if (!c)
@@ -2722,6 +2748,7 @@ int mosrx_fwd_set(mosrx_ctx *c, const mosrx_fwd_tables *t)
 		return -EINVAL;
 	if (!t) {
 		c->d_fwd = NULL;
+		c->fwd_num_netdevs = 0;
 		return 0;
 	}
 	if (t->num_routes > MOSRX_FWD_MAX_ROUTES || t->num_arp > MOSRX_FWD_MAX_ARP ||
@@ -2770,6 +2797,7 @@ int mosrx_fwd_set(mosrx_ctx *c, const mosrx_fwd_tables *t)
 	if (rc)
 		return rc;
 	c->d_fwd = c->d_fwd_pool[k];
+	c->fwd_num_netdevs = t->num_netdevs;
 	c->fwd_pool_next = (k + 1) % MOSRX_FWD_POOL;
 	return 0;
 }
@@ -2858,6 +2886,52 @@ int mosrx_fwd_build_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_p
 	HIPCHK(hipSetDevice(c->device));
 	fwd_mark_used(c);
 	rc = mosrx_launch_fwd_build(&fp, (void *)s);
+	mosrx__note_stream(c, s);
+	return rc;
+}
+
+int mosrx_fwd_build_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint8_t *d_tx_frames,
+                              uint64_t ring_cap, uint32_t nrings, uint32_t *d_tx_off, uint16_t *d_tx_len,
+                              uint32_t *d_tx_src, mosrx_fwd_ring *d_rings, void *d_scratch, size_t scratch_bytes,
+                              void *stream)
+{
+	mosrx_fparams fp;
+	mosrx_rparams rp;
+	hipStream_t s;
+	int rc;
+	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || !d_tx_frames || ((uintptr_t)d_tx_frames & 15) || !d_tx_off ||
+	    ((uintptr_t)d_tx_off & 3) || !d_tx_len || ((uintptr_t)d_tx_len & 1) || !d_tx_src || ((uintptr_t)d_tx_src & 3) ||
+	    !d_rings || ((uintptr_t)d_rings & 15) || !d_scratch || ((uintptr_t)d_scratch & 15) || nrings < 1 ||
+	    nrings > MOSRX_FWD_MAX_NETDEVS || (ring_cap & 15) || ring_cap > (1ull << 32) ||
+	    ring_cap * nrings > (1ull << 32) /* tx_off is a u32 */ ||
+	    scratch_bytes < mosrx_fwd_rings_scratch_bytes(b->n, nrings))
+		return -EINVAL;
+	if ((rc = fwd_batch(c, b, &fp)))
+		return rc;
+	if (!c->d_fwd)
+		return -ENOENT;
+	if (nrings < c->fwd_num_netdevs)
+		return -EINVAL;
+	memset(&rp, 0, sizeof(rp));
+	rp.frames = fp.frames;
+	rp.off = fp.off;
+	rp.tab = fp.tab;
+	rp.plan = d_plan;
+	rp.frames_bytes = fp.frames_bytes;
+	rp.n = fp.n;
+	rp.nrings = nrings;
+	rp.cap_units = (uint32_t)(ring_cap / 16);
+	rp.tiles = (b->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+	rp.tx = d_tx_frames;
+	rp.tx_off = d_tx_off;
+	rp.tx_len = d_tx_len;
+	rp.tx_src = d_tx_src;
+	rp.rings = d_rings;
+	rp.scratch = (uint32_t *)d_scratch;
+	s = stream ? (hipStream_t)stream : c->stream;
+	HIPCHK(hipSetDevice(c->device));
+	fwd_mark_used(c);
+	rc = mosrx_launch_fwd_rings(&rp, (void *)s);
 	mosrx__note_stream(c, s);
 	return rc;
 }

@@ -154,11 +154,13 @@ struct mosrx_ctx {
 	int fwd_pool_used[MOSRX_FWD_POOL];
 	uint32_t fwd_pool_next;
 	uint32_t fwd_listener;           /* mosrx_fwd_set_listener */
-	/* MOSRX_OP_FWD's own TX outputs + scratch, one block of fwd_tmp_stride bytes
-	 * per timing stream and one for the context stream (mosrx_time_op) */
+	uint32_t fwd_num_netdevs;        /* the installed tables' num_netdevs (the ring build's least nrings) */
+	/* MOSRX_OP_FWD's / MOSRX_OP_FWD_RINGS' own TX outputs + scratch, one block of
+	 * fwd_tmp_stride bytes per timing stream and one for the context stream
+	 * (mosrx_time_op); fwd_tmp_rings rings of fwd_tmp_cap bytes (MOSRX_OP_FWD: 1) */
 	uint8_t *fwd_tmp;
 	size_t fwd_tmp_stride, fwd_tmp_bytes, fwd_tmp_cap;
-	uint32_t fwd_tmp_n;
+	uint32_t fwd_tmp_n, fwd_tmp_rings;
 };
 
 int mosrx__check_batch(const mosrx_batch *b, int dev);

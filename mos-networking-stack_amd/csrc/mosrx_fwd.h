@@ -67,6 +67,31 @@ typedef struct mosrx_fparams {
 int mosrx_launch_fwd_plan(const mosrx_fparams *fp, void *stream);
 int mosrx_launch_fwd_build(const mosrx_fparams *fp, void *stream);
 
+/* The ring form of the build (mosrx_fwd_build_rings_dev): its own parameters,
+ * so the launches above are passed what they always were.  Scratch is one row
+ * per tile of nrings entries of MOSRX_FWD_ROW bytes: {units, sent, 0, 0} after
+ * the totals launch, {unit base lo, hi, entry base, 0} after the scan. */
+typedef struct mosrx_rparams {
+	const uint8_t  *frames;
+	const uint32_t *off;
+	const mosrx_fwd_dev *tab;
+	const mosrx_fwd *plan;       /* n, 8-byte aligned */
+	uint32_t frames_bytes, n;
+	uint32_t nrings;             /* 1 .. MOSRX_FWD_MAX_NETDEVS */
+	uint32_t cap_units;          /* ring_cap / 16; nrings * cap_units <= 2^28 */
+	uint32_t tiles;
+	uint8_t  *tx;                /* 16-byte aligned: nrings rings of cap_units units */
+	uint32_t *tx_off;
+	uint16_t *tx_len;
+	uint32_t *tx_src;
+	mosrx_fwd_ring *rings;       /* nrings, 16-byte aligned */
+	uint32_t *scratch;           /* max(tiles, 1) * nrings rows */
+} mosrx_rparams;
+
+/* Its three launches (totals, scan, copy) on `stream`; 0, -EINVAL or -EIO.
+ * n == 0: the scan alone (rings[q] = {0, 0, 0, 0}). */
+int mosrx_launch_fwd_rings(const mosrx_rparams *rp, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,12 +118,16 @@ BPF_MAX_PROGS = 32
 # ---- forwarding (include/mosrx.h: mosrx_fwd_tables, mosrx_fwd) ----
 OP_FWD_PLAN = 10       # MOSRX_OP_FWD_PLAN: the forwarding plan (arg = rec_bytes | in_ifidx << 8)
 OP_FWD = 11            # MOSRX_OP_FWD: plan + build
+OP_FWD_RINGS = 12      # MOSRX_OP_FWD_RINGS: plan + the ring form of the build (one ring per netdev)
 FWD_MAX_ROUTES, FWD_MAX_ARP, FWD_MAX_NETDEVS = 128, 1024, 16
 FWD_NONE, FWD_IP, FWD_ETH, FWD_NO_ROUTE, FWD_NO_ARP, FWD_NO_NIC = range(6)   # MOSRX_FWD_*
 # mosrx_fwd: the plan of one frame
 FWD_DTYPE = np.dtype([("tx_len", "<u2"), ("out_ifidx", "i1"), ("kind", "u1"), ("arp_idx", "<u2"),
                       ("reserved", "<u2")])
 assert FWD_DTYPE.itemsize == 8
+# mosrx_fwd_ring: one TX ring (output netdev) of mosrx_fwd_build_rings_dev
+FWD_RING_DTYPE = np.dtype([("start", "<u4"), ("count", "<u4"), ("dropped", "<u4"), ("units", "<u4")])
+assert FWD_RING_DTYPE.itemsize == 16
 
 
 class FwdRoute(C.Structure):
@@ -468,6 +472,8 @@ def lib():
             "mosrx_fwd_plan_dev": (I, [P, C.POINTER(Batch), P, I, I, P, P]),
             "mosrx_fwd_build_dev": (I, [P, C.POINTER(Batch), P, P, U64, P, P, P, P, P, P, C.c_size_t, P]),
             "mosrx_fwd_scratch_bytes": (C.c_size_t, [U32]),
+            "mosrx_fwd_build_rings_dev": (I, [P, C.POINTER(Batch), P, P, U64, U32, P, P, P, P, P, C.c_size_t, P]),
+            "mosrx_fwd_rings_scratch_bytes": (C.c_size_t, [U32, U32]),
             "mosrx_fwd_tile": (U32, []),
             "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
             "mosrx_hub_endpoint": (P, [P, U32]),
@@ -993,6 +999,17 @@ class Context:
         if sync:
             _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
 
+    def fwd_build_rings_dev(self, b: Batch, d_plan: int, d_tx_frames: int, ring_cap: int, nrings: int, d_tx_off: int,
+                            d_tx_len: int, d_tx_src: int, d_rings: int, d_scratch: int, scratch_bytes: int,
+                            sync: bool = True, stream: int | None = None) -> None:
+        """mosrx_fwd_build_rings_dev: the TX frames of a planned batch, each in the ring
+        of its output netdev (d_rings: nrings records of FWD_RING_DTYPE)."""
+        _chk(lib().mosrx_fwd_build_rings_dev(self.handle, C.byref(b), d_plan, d_tx_frames, ring_cap, nrings, d_tx_off,
+                                             d_tx_len, d_tx_src, d_rings, d_scratch, scratch_bytes, stream),
+             "mosrx_fwd_build_rings_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
     def slot_steer(self, slot: int, idx: list | None, qstart: list | None) -> None:
         """mosrx_slot_steer: arm the slot's next group submit (host pointers per
         batch: n indices, STEER_QSLOTS queue starts); None, None disarms."""
@@ -1114,18 +1131,18 @@ class Context:
                 d.d_match = DevBuffer(self, max(d.n * 4, 4))
             if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) and d.d_sidx is None:
                 d.d_sidx = DevBuffer(self, max(d.n * 4, 4))
-            if op in (OP_FWD_PLAN, OP_FWD) and d.d_fplan is None:
+            if op in (OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS) and d.d_fplan is None:
                 d.d_fplan = DevBuffer(self, max(d.n * 8, 8))
         bs = (Batch * len(dbs))(*[d.batch() for d in dbs])
         # OP_STEER reads the records a classify call left: the compact ones for arg == 8
         outs = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_BPF else
                                           d.d_out8.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE,
-                                                                 OP_FWD_PLAN, OP_FWD) and (arg & 0xFF) == 8
+                                                                 OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS) and (arg & 0xFF) == 8
                                           else d.d_out.ptr) for d in dbs])
         aux = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_CLASSIFY_BPF else
                                          d.d_tinfo.ptr if op == OP_CLASSIFY_TI else
                                          d.d_sidx.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) else
-                                         d.d_fplan.ptr if op in (OP_FWD_PLAN, OP_FWD) else
+                                         d.d_fplan.ptr if op in (OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS) else
                                          (d.d_fhash.ptr if d.d_fhash else None)) for d in dbs])
         tot, avg = C.c_float(), C.c_float()
         _chk(lib().mosrx_time_op(self.handle, op, arg, bs, len(dbs), outs, aux, iters, nstreams,
