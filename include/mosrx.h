@@ -505,6 +505,49 @@ int    mosrx_fwd_build_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx
 /* Scratch a ring build needs (no GPU needed; never 0, non-decreasing in both). */
 size_t mosrx_fwd_rings_scratch_bytes(uint32_t n, uint32_t nrings);
 
+/* Forwarding attached to a batch queue, the way steering is: every
+ * mosrx_queue_run then enqueues, behind the classify launch (and the steer
+ * launches) on the same stream, one plan launch over every batch of the queue
+ * and, with TX outputs given, the ring build's three launches over every
+ * batch: four launches per run whatever nb is.  Batch i's outputs are byte
+ * for byte what mosrx_fwd_plan_dev + mosrx_fwd_build_rings_dev write for that
+ * batch alone under the same tables, ring_cap and nrings.  The records read
+ * are the queue's own (8-byte with MOSRX_QUEUE_COMPACT, else 16-byte).
+ *   in_ifidx     nb input netdevs, 0 .. MOSRX_FWD_MAX_NETDEVS - 1; NULL: all 0
+ *   d_plan       nb plan arrays, d_plan[i]: n_i entries, 8-byte aligned (NULL
+ *                allowed for an empty batch only)
+ *   ring_cap, nrings   as mosrx_fwd_build_rings_dev, the same for every batch
+ *   d_tx_frames  nb ring blocks of nrings * ring_cap bytes, 16-byte aligned
+ *   d_tx_off, d_tx_len, d_tx_src   n_i entries each
+ *   d_rings      d_rings[i][nrings], 16-byte aligned; required for empty
+ *                batches too, and written {0, 0, 0, 0} for them
+ * The five TX pointer arrays are all NULL (plan only: ring_cap and nrings are
+ * not looked at) or all non-NULL.  f == NULL detaches: the queue runs exactly
+ * as before.  Not while a run of the queue is in flight.  The queue's device
+ * table and scratch (a row of MOSRX_FWD_ROW bytes per tile and ring) are
+ * allocated at the first attach that needs them and freed by
+ * mosrx_queue_destroy.  -EINVAL (the queue keeps the attachment it had): a
+ * NULL or misaligned pointer of a non-empty batch, an in_ifidx out of range,
+ * half a set of TX arrays, nrings outside 1 .. MOSRX_FWD_MAX_NETDEVS, ring_cap
+ * not a multiple of 16 or nrings * ring_cap > 2^32.
+ * The tables, forward, num_msp and the listener flag are those in effect at
+ * each run, as for mosrx_fwd_plan_dev.  A run of a queue with forwarding
+ * attached checks before it launches anything: -ENOENT with no tables
+ * installed, -EINVAL with TX outputs attached and nrings below the installed
+ * tables' num_netdevs; nothing is enqueued then, not even the classify launch. */
+typedef struct mosrx_queue_fwd {
+	const uint8_t *in_ifidx;
+	mosrx_fwd *const *d_plan;
+	uint64_t  ring_cap;
+	uint32_t  nrings;
+	uint8_t        *const *d_tx_frames;
+	uint32_t       *const *d_tx_off;
+	uint16_t       *const *d_tx_len;
+	uint32_t       *const *d_tx_src;
+	mosrx_fwd_ring *const *d_rings;
+} mosrx_queue_fwd;
+int mosrx_queue_set_fwd(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd *f);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned

@@ -2259,6 +2259,14 @@ struct mosrx_queue {
 	/* ... and its side form (mosrx_queue_set_steer_gather_side), the third table */
 	mosrx_xdesc *d_xdesc;
 	int side;
+	/* forwarding (mosrx_queue_set_fwd): the batches' table and the build's
+	 * scratch rows, allocated at the first attach that needs them; fwd: a plan
+	 * attached, fwd_build: with the ring build */
+	mosrx_fdesc *d_fdesc;
+	uint32_t *d_fscratch;
+	size_t fscratch_rows;
+	uint32_t fwd_tiles, fwd_nrings, fwd_cap_units;
+	int fwd, fwd_build;
 };
 
 int mosrx_queue_create_ex(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, void *const *d_out,
@@ -2378,12 +2386,12 @@ static int queue_classify(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 	return 0;
 }
 
-int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
+static int queue_fwd_check(const mosrx_ctx *c, const mosrx_queue *q);
+static int queue_fwd(mosrx_ctx *c, const mosrx_queue *q, void *stream);
+
+static int queue_steer(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 {
 	mosrx_sparams sp;
-	int rc = queue_classify(c, q, stream);
-	if (rc || !q->steer)
-		return rc;
 	memset(&sp, 0, sizeof(sp));
 	sp.desc = q->d_sdesc;
 	sp.hist = q->d_shist;
@@ -2399,6 +2407,19 @@ int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 		sp.side = 1;
 	}
 	return steer_launch(c, &sp, q->steer_maxn, stream ? stream : (void *)c->stream);
+}
+
+int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
+{
+	int rc;
+	/* forwarding's run-time conditions first: a run that cannot forward enqueues nothing */
+	if (c && q && q->fwd && (rc = queue_fwd_check(c, q)))
+		return rc;
+	if ((rc = queue_classify(c, q, stream)))
+		return rc;
+	if (q->steer && (rc = queue_steer(c, q, stream)))
+		return rc;
+	return q->fwd ? queue_fwd(c, q, stream) : 0;
 }
 
 static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
@@ -2671,6 +2692,10 @@ void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 		hipFree(q->d_xdesc);
 	if (q->d_shist)
 		hipFree(q->d_shist);
+	if (q->d_fdesc)
+		hipFree(q->d_fdesc);
+	if (q->d_fscratch)
+		hipFree(q->d_fscratch);
 	free(q->h_desc);
 	free(q->d_match);
 	free(q);
@@ -2934,4 +2959,132 @@ int mosrx_fwd_build_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fw
 	rc = mosrx_launch_fwd_rings(&rp, (void *)s);
 	mosrx__note_stream(c, s);
 	return rc;
+}
+
+/* ---- forwarding over a batch queue (mosrx_queue_set_fwd) ---- */
+
+static int queue_fwd_check(const mosrx_ctx *c, const mosrx_queue *q)
+{
+	if (!c->d_fwd)
+		return -ENOENT;
+	if (q->fwd_build && q->fwd_nrings < c->fwd_num_netdevs)
+		return -EINVAL;
+	return 0;
+}
+
+/* The plan launch and, with TX outputs attached, the build's three, behind
+ * whatever the run already put on the stream. */
+static int queue_fwd(mosrx_ctx *c, const mosrx_queue *q, void *stream)
+{
+	mosrx_fqparams fq;
+	const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+	int rc;
+	memset(&fq, 0, sizeof(fq));
+	fq.desc = q->d_fdesc;
+	fq.tab = c->d_fwd;
+	fq.scratch = q->d_fscratch;
+	fq.nb = q->nb;
+	fq.total_tiles = q->fwd_tiles;
+	fq.rec_bytes = q->compact ? 8u : 16u;
+	fq.forward = c->params.forward;
+	fq.num_msp = c->params.num_msp;
+	fq.listener = c->fwd_listener;
+	fq.nrings = q->fwd_nrings;
+	fq.cap_units = q->fwd_cap_units;
+	HIPCHK(hipSetDevice(c->device));
+	fwd_mark_used(c);
+	rc = mosrx_launch_fwd_queue(&fq, q->fwd_build, (void *)s);
+	mosrx__note_stream(c, s);   /* (after the launches: its event covers them) */
+	return rc;
+}
+
+int mosrx_queue_set_fwd(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd *f)
+{
+	mosrx_fdesc *h;
+	uint32_t i, tiles = 0;
+	size_t rows;
+	int build;
+	if (!c || !q)
+		return -EINVAL;
+	if (!f) {
+		q->fwd = q->fwd_build = 0;
+		return 0;
+	}
+	build = f->d_tx_frames || f->d_tx_off || f->d_tx_len || f->d_tx_src || f->d_rings;
+	if (!f->d_plan || (build && (!f->d_tx_frames || !f->d_tx_off || !f->d_tx_len || !f->d_tx_src || !f->d_rings)))
+		return -EINVAL;
+	if (build && (f->nrings < 1 || f->nrings > MOSRX_FWD_MAX_NETDEVS || (f->ring_cap & 15) ||
+	              f->ring_cap > (1ull << 32) || f->ring_cap * f->nrings > (1ull << 32) /* tx_off is a u32 */))
+		return -EINVAL;
+	for (i = 0; i < q->nb; i++) {
+		if (f->in_ifidx && f->in_ifidx[i] >= MOSRX_FWD_MAX_NETDEVS)
+			return -EINVAL;
+		if (build && (!f->d_rings[i] || ((uintptr_t)f->d_rings[i] & 15)))
+			return -EINVAL;
+		if (!q->h_desc[i].n)
+			continue;
+		if (!f->d_plan[i] || ((uintptr_t)f->d_plan[i] & 7) || ((uintptr_t)q->h_desc[i].off & 3) ||
+		    ((uintptr_t)q->h_desc[i].len & 1))
+			return -EINVAL;
+		if (build && (!f->d_tx_frames[i] || ((uintptr_t)f->d_tx_frames[i] & 15) || !f->d_tx_off[i] ||
+		              ((uintptr_t)f->d_tx_off[i] & 3) || !f->d_tx_len[i] || ((uintptr_t)f->d_tx_len[i] & 1) ||
+		              !f->d_tx_src[i] || ((uintptr_t)f->d_tx_src[i] & 3)))
+			return -EINVAL;
+	}
+	if (!(h = calloc(q->nb, sizeof(*h))))
+		return -ENOMEM;
+	for (i = 0; i < q->nb; i++) {
+		const mosrx_qdesc *d = &q->h_desc[i];
+		h[i].n = d->n;
+		h[i].tile_base = tiles;
+		h[i].in_ifidx = f->in_ifidx ? f->in_ifidx[i] : 0;
+		h[i].rings = build ? f->d_rings[i] : NULL;
+		tiles += (d->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+		if (!d->n)
+			continue;
+		h[i].frames = d->frames;
+		h[i].off = d->off;
+		h[i].len = d->len;
+		h[i].rec = (const uint8_t *)d->out;
+		h[i].frames_bytes = d->frames_bytes;
+		h[i].plan = f->d_plan[i];
+		if (build) {
+			h[i].tx = f->d_tx_frames[i];
+			h[i].tx_off = f->d_tx_off[i];
+			h[i].tx_len = f->d_tx_len[i];
+			h[i].tx_src = f->d_tx_src[i];
+		}
+	}
+	q->fwd = q->fwd_build = 0;
+	rows = build ? ((size_t)tiles ? tiles : 1) * f->nrings : 0;
+	if (hipSetDevice(c->device) != hipSuccess) {
+		free(h);
+		return -EIO;
+	}
+	if (rows > q->fscratch_rows) {
+		if (q->d_fscratch)
+			hipFree(q->d_fscratch);
+		q->d_fscratch = NULL;
+		q->fscratch_rows = 0;
+		if (hipMalloc((void **)&q->d_fscratch, rows * MOSRX_FWD_ROW) != hipSuccess) {
+			free(h);
+			return -ENOMEM;
+		}
+		q->fscratch_rows = rows;
+	}
+	if (!q->d_fdesc && hipMalloc((void **)&q->d_fdesc, (size_t)q->nb * sizeof(*h)) != hipSuccess) {
+		free(h);
+		return -ENOMEM;
+	}
+	if (hipMemcpy(q->d_fdesc, h, (size_t)q->nb * sizeof(*h), hipMemcpyHostToDevice) != hipSuccess) {
+		free(h);
+		return -EIO;
+	}
+	free(h);
+	q->fwd_tiles = tiles;
+	q->fwd_nrings = build ? f->nrings : 0;
+	q->fwd_cap_units = build ? (uint32_t)(f->ring_cap / 16) : 0;
+	q->fwd_build = build;
+	q->fwd = 1;
+	return 0;
 }

@@ -92,6 +92,53 @@ typedef struct mosrx_rparams {
  * n == 0: the scan alone (rings[q] = {0, 0, 0, 0}). */
 int mosrx_launch_fwd_rings(const mosrx_rparams *rp, void *stream);
 
+/* The batch-queue form (mosrx_queue_set_fwd): one device-resident descriptor
+ * per batch of the queue.  Tiles of MOSRX_FWD_TILE frames never straddle
+ * batches, so one tile_base[] serves the plan, totals and copy launches (grid =
+ * total_tiles, a workgroup finding its batch by binary search of tile_base[]
+ * as the steer queue form does), and a batch's scratch rows start at
+ * tile_base * nrings.  An empty batch occupies no tile (its tile_base is its
+ * successor's) and its pointers other than rings may be NULL. */
+typedef struct mosrx_fdesc {
+	const uint8_t  *frames;
+	const uint32_t *off;
+	const uint16_t *len;
+	const uint8_t  *rec;         /* n records of the launch's rec_bytes */
+	mosrx_fwd      *plan;        /* n, 8-byte aligned */
+	uint8_t        *tx;          /* the five TX outputs of mosrx_rparams; unused by a plan-only launch */
+	uint32_t       *tx_off;
+	uint16_t       *tx_len;
+	uint32_t       *tx_src;
+	mosrx_fwd_ring *rings;
+	uint32_t frames_bytes, n;
+	uint32_t in_ifidx;           /* 0 .. MOSRX_FWD_MAX_NETDEVS - 1 */
+	uint32_t tile_base;          /* the batch's first tile = its first workgroup in the tiled launches */
+} mosrx_fdesc;
+
+typedef struct mosrx_fqparams {
+	const mosrx_fdesc   *desc;   /* nb, device-resident */
+	const mosrx_fwd_dev *tab;
+	uint32_t *scratch;           /* max(total_tiles, 1) * nrings rows of MOSRX_FWD_ROW bytes; plan only: unused */
+	uint32_t nb, total_tiles;
+	uint32_t rec_bytes;          /* 8 or 16 */
+	int32_t  forward;            /* mosrx_mos_forwards' parameters */
+	uint32_t num_msp, listener;
+	uint32_t nrings;             /* 1 .. MOSRX_FWD_MAX_NETDEVS */
+	uint32_t cap_units;          /* ring_cap / 16; nrings * cap_units <= 2^28 */
+} mosrx_fqparams;
+
+#ifdef __cplusplus
+static_assert(sizeof(mosrx_fdesc) == 96 && sizeof(mosrx_fqparams) == 56, "queue form: 96-byte descriptor, 56-byte parameters");
+#else
+_Static_assert(sizeof(mosrx_fdesc) == 96 && sizeof(mosrx_fqparams) == 56, "queue form: 96-byte descriptor, 56-byte parameters");
+#endif
+
+/* The plan launch over every batch of the queue and, with_build, the ring
+ * build's three (totals, scan with one workgroup per batch, copy) on `stream`:
+ * four launches whatever nb is; 0, -EINVAL or -EIO.  Allocates nothing.  A
+ * queue of empty batches launches the scan alone (every rings[q] = {0,0,0,0}). */
+int mosrx_launch_fwd_queue(const mosrx_fqparams *fq, int with_build, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

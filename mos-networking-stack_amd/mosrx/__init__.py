@@ -147,6 +147,13 @@ class FwdTables(C.Structure):
                 ("arp", FwdArp * FWD_MAX_ARP)]
 
 
+class QueueFwd(C.Structure):
+    """mosrx_queue_fwd: forwarding outputs attached to a batch queue (Queue.set_fwd)."""
+    _fields_ = [("in_ifidx", C.c_void_p), ("d_plan", C.c_void_p), ("ring_cap", C.c_uint64), ("nrings", C.c_uint32),
+                ("d_tx_frames", C.c_void_p), ("d_tx_off", C.c_void_p), ("d_tx_len", C.c_void_p),
+                ("d_tx_src", C.c_void_p), ("d_rings", C.c_void_p)]
+
+
 def conf_mask(prefix: int) -> int:
     """htonl((prefix == 0) ? 0 : ((-1) << (32 - prefix))) as config.c:316, :346 store it
     (network order, the raw u32 of a little-endian host)."""
@@ -475,6 +482,7 @@ def lib():
             "mosrx_fwd_build_rings_dev": (I, [P, C.POINTER(Batch), P, P, U64, U32, P, P, P, P, P, C.c_size_t, P]),
             "mosrx_fwd_rings_scratch_bytes": (C.c_size_t, [U32, U32]),
             "mosrx_fwd_tile": (U32, []),
+            "mosrx_queue_set_fwd": (I, [P, P, C.POINTER(QueueFwd)]),
             "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
             "mosrx_hub_endpoint": (P, [P, U32]),
             "mosrx_hub_stats_get": (I, [P, P]),
@@ -1274,6 +1282,22 @@ class Queue:
                 for a in (idx, qstart, qrec, qoff, qlen, qfhash, qmatch)]
         _chk(lib().mosrx_queue_set_steer_gather_side(self.ctx.handle, self.handle, *arrs),
              "mosrx_queue_set_steer_gather_side")
+
+    def set_fwd(self, plan: list | None, in_ifidx: list | None = None, ring_cap: int = 0, nrings: int = 0,
+                tx_frames: list | None = None, tx_off: list | None = None, tx_len: list | None = None,
+                tx_src: list | None = None, rings: list | None = None) -> None:
+        """mosrx_queue_set_fwd: attach forwarding to every run -- per-batch device
+        pointers for the plan arrays and, for the ring build, the five TX outputs
+        (all or none); in_ifidx: per-batch input netdevs (None: all 0).  plan None detaches."""
+        if plan is None:
+            _chk(lib().mosrx_queue_set_fwd(self.ctx.handle, self.handle, None), "mosrx_queue_set_fwd")
+            return
+        keep = [(C.c_void_p * len(a))(*a) if a is not None else None
+                for a in (plan, tx_frames, tx_off, tx_len, tx_src, rings)]
+        ifs = (C.c_uint8 * len(in_ifidx))(*in_ifidx) if in_ifidx is not None else None
+        f = QueueFwd(C.cast(ifs, C.c_void_p), C.cast(keep[0], C.c_void_p), ring_cap, nrings,
+                     *[C.cast(a, C.c_void_p) for a in keep[1:]])
+        _chk(lib().mosrx_queue_set_fwd(self.ctx.handle, self.handle, C.byref(f)), "mosrx_queue_set_fwd")
 
     def run(self, sync: bool = True):
         _chk(lib().mosrx_queue_run(self.ctx.handle, self.handle, None), "mosrx_queue_run")
