@@ -1145,8 +1145,12 @@ __device__ __forceinline__ void classify_span_stream(const mosrx_kparams &kp, ui
 	uint32_t ld = kp.len[q];
 	asm volatile("" : "+v"(ld));   // keep the len[] load unconditional (not sunk into a branch)
 	const uint32_t o = active ? od : 0u, cap = active ? eff_caplen(od, ld, nbytes) : 0u;
-	// speculative tail bounds from the capture length: [split, off + caplen)
-	const uint32_t lo_l = (o + (uint32_t)WEND) & ~15u;
+	// speculative tail bounds from the capture length: [split, off + caplen).
+	// A split that wraps past 2^32 (a bogus offset in the last WEND bytes of the
+	// address range) is no tail: wrapped it would lie below hi_l, and the
+	// streamers' loops count from it up to hi_l in steps that then wrap too.
+	const uint32_t sp_l = o + (uint32_t)WEND;
+	const uint32_t lo_l = sp_l < o ? 0xFFFFFFFFu : sp_l & ~15u;
 	const uint32_t hi_l = active ? o + cap : 0u;
 	// buffer order: the next frame starts at or after this capture's end
 	const uint32_t onext = (uint32_t)__shfl_down((int)o, 1);

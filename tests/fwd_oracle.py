@@ -79,21 +79,32 @@ def get_destination_hwaddr(T, dip):
     return idx
 
 
+def capture(off, ln, frames_bytes):
+    """A frame's capture inside the batch buffer (include/mosrx.h, mosrx_batch.frames_bytes:
+    no frame byte is read at or past it): min(len, max(frames_bytes - off, 0))."""
+    room = np.maximum(int(frames_bytes) - np.asarray(off, np.uint32).astype(np.int64), 0)
+    return np.minimum(np.asarray(ln, np.uint16).astype(np.int64), room)
+
+
 def _field(frames, off, ln, at, nbytes):
-    """Frame bytes at..at+nbytes per frame (zeros where the capture ends before them)."""
+    """Frame bytes at..at+nbytes per frame (zeros where the capture ends before them);
+    `ln` is the capture, so no index passes the buffer."""
     out = np.zeros((len(off), nbytes), np.uint8)
-    ok = ln.astype(np.int64) >= at + nbytes
+    ok = np.asarray(ln).astype(np.int64) >= at + nbytes
     pos = off.astype(np.int64)[ok, None] + at + np.arange(nbytes)
     out[ok] = frames[pos]
     return out, ok
 
 
-def plan(frames, off, ln, reason, t, in_ifidx, forward=1, num_msp=1, listener=False):
-    """One mosrx.FWD_DTYPE record per frame."""
+def plan(frames, off, ln, reason, t, in_ifidx, forward=1, num_msp=1, listener=False, frames_bytes=None):
+    """One mosrx.FWD_DTYPE record per frame.  frames_bytes (default: the buffer's
+    length) ends the batch buffer: a frame is what `capture` leaves of it."""
     T = tables_np(t)
     frames = np.asarray(frames, np.uint8)
     off = np.asarray(off, np.uint32)
-    ln = np.asarray(ln, np.uint16)
+    frames_bytes = len(frames) if frames_bytes is None else int(frames_bytes)
+    assert 0 <= frames_bytes <= len(frames)
+    ln = capture(off, ln, frames_bytes)
     n = len(off)
     out = np.zeros(n, mosrx.FWD_DTYPE)
     out["out_ifidx"] = -1
@@ -107,7 +118,7 @@ def plan(frames, off, ln, reason, t, in_ifidx, forward=1, num_msp=1, listener=Fa
         out["kind"][e] = NO_NIC
     else:
         out["kind"][e] = ETH
-        out["tx_len"][e] = ln[e]
+        out["tx_len"][e] = ln[e].astype(np.uint16)
         out["out_ifidx"][e] = nicout
     # ForwardIPPacket
     tl, ok1 = _field(frames, off, ln, 16, 2)

@@ -70,10 +70,10 @@ def cap_for(pl):
 class Run:
     """One batch on the GPU: classify, plan, build; download everything."""
 
-    def __init__(self, ctx, buf, off, ln, rec_bytes=16):
+    def __init__(self, ctx, buf, off, ln, rec_bytes=16, frames_bytes=None):
         self.ctx, self.buf, self.off, self.ln, self.rb = ctx, buf, off, ln, rec_bytes
         self.n = len(off)
-        self.db = ctx.upload(buf, off, ln)
+        self.db = ctx.upload(buf, off, ln, frames_bytes=frames_bytes)
         if rec_bytes == 16:
             ctx.classify_dev(self.db)
             self.d_rec = self.db.d_out

@@ -159,6 +159,73 @@ def test_fixture_covers_the_walks():
     assert np.bincount(z["conv_nicfwd__plan"]["kind"], minlength=6)[F.ETH] > 0
 
 
+def test_frames_bytes_default_changes_nothing():
+    """frames_bytes left out is the buffer's length: every plan is what it was
+    (mOS's own in fwd_plan.npz, the hand-worked one, the golden frame sets), and
+    no descriptor of those sets, bogus ones included, makes _field index past the buffer."""
+    z = load_golden()
+    for name in sorted(P.SCENARIOS):
+        k = name + "__"
+        t = golden_tables(z, name)
+        args = (z[k + "frames"], z[k + "off"], z[k + "len"], z[k + "reason"], t, 0)
+        np.testing.assert_array_equal(F.plan(*args), z[k + "plan"])
+        np.testing.assert_array_equal(F.plan(*args, frames_bytes=len(z[k + "frames"])), z[k + "plan"])
+    buf, off, ln = pack_frames(frames3(), phase=5)
+    reason = np.array([R["TCP_OK"], R["NON_IPV4"], R["TCP_OK"]], np.uint8)
+    tn = mosrx.fwd_tables(netdevs=["02:00:00:00:00:a0", "02:00:00:00:00:a1"], nic_fwd={0: 1})
+    for pl in (F.plan(buf, off, ln, reason, tn, 0), F.plan(buf, off, ln, reason, tn, 0, frames_bytes=len(buf))):
+        assert pl["kind"].tolist() == [F.IP, F.ETH, F.IP] and pl["tx_len"].tolist() == [57, 61, 60]
+    for fix in ("edge", "rand_small"):
+        g = np.load(os.path.join(GOLDEN, f"{fix}.npz"))
+        # frames inside the buffer: the capture is len[], the rule the restatement had before
+        inside = g["off"].astype(np.int64) + g["len"] <= len(g["frames"])
+        reason = np.where(inside, R["NON_IPV4"], R["TRUNCATED"]).astype(np.uint8)
+        pl = F.plan(g["frames"], g["off"], g["len"], reason, tn, 0)
+        np.testing.assert_array_equal(pl["tx_len"][inside & (g["len"] >= 14)], g["len"][inside & (g["len"] >= 14)])
+        assert not pl["kind"][~inside].any()
+
+
+def test_frames_bytes_by_hand():
+    """Four descriptors over a 200-byte buffer that ends, for the batch, at byte 140:
+    a 60-byte frame ending exactly there, one cut to 40 bytes, one starting at
+    the end and one at 0xFFFFFFF0 (off + len wraps)."""
+    ipb = bytes.fromhex("02d000000001" "025000000001" "0800") + \
+        bytes.fromhex("4500002e" "00000000" "40fd0000" "0a000001" "0a010203") + bytes(26)   # tot_len 46, payload zeros
+    assert len(ipb) == 60
+    buf = np.full(200, 0xAB, np.uint8)
+    buf[80:140] = np.frombuffer(ipb, np.uint8)
+    off = np.array([80, 100, 140, 0xFFFFFFF0], np.uint32)
+    ln = np.full(4, 60, np.uint16)
+    np.testing.assert_array_equal(F.capture(off, ln, 140), [60, 40, 0, 0])
+    np.testing.assert_array_equal(F.capture(off, ln, 139), [59, 39, 0, 0])
+    tn = mosrx.fwd_tables(netdevs=["02:00:00:00:00:a0", "02:00:00:00:00:a1"], nic_fwd={0: 1})
+    eth = np.full(4, R["NON_IPV4"], np.uint8)
+    tcp = np.full(4, R["TCP_OK"], np.uint8)
+    # the same answers from frames_bytes = 140 and from a buffer that is 140 bytes long
+    for fr, kw in ((buf, dict(frames_bytes=140)), (buf[:140], {})):
+        pl = F.plan(fr, off, ln, eth, tn, 0, **kw)
+        assert pl["kind"].tolist() == [F.ETH, F.ETH, F.NONE, F.NONE]
+        assert pl["tx_len"].tolist() == [60, 40, 0, 0] and pl["out_ifidx"].tolist() == [1, 1, -1, -1]
+        # as IPv4: the whole packet (14 + 46) lies inside the first capture; the second
+        # reads tot_len 0 from the first's payload: not a packet
+        pl = F.plan(fr, off, ln, tcp, tn, 0, **kw)
+        assert pl["kind"].tolist() == [F.IP, F.NONE, F.NONE, F.NONE] and pl["tx_len"].tolist() == [60, 0, 0, 0]
+    # one byte less: the packet passes the capture (whatever the record says); as Ethernet it goes out cut
+    assert not F.plan(buf, off, ln, tcp, tn, 0, frames_bytes=139)["kind"].any()
+    pl = F.plan(buf, off, ln, eth, tn, 0, frames_bytes=139)
+    assert pl["kind"].tolist() == [F.ETH, F.ETH, F.NONE, F.NONE] and pl["tx_len"].tolist() == [59, 39, 0, 0]
+    # a capture under an Ethernet header is not forwarded: 80 + 13, and nothing at all
+    assert F.plan(buf, off, ln, eth, tn, 0, frames_bytes=93)["kind"].tolist() == [F.NONE] * 4
+    assert F.plan(buf, off, ln, eth, tn, 0, frames_bytes=94)["tx_len"].tolist() == [14, 0, 0, 0]
+    assert not F.plan(buf, off, ln, eth, tn, 0, frames_bytes=0)["kind"].any()
+    # the TX bytes of the cut frame are the captured ones only
+    z = lambda n, d: np.frombuffer(b"\xEE" * (n * np.dtype(d).itemsize), d).copy()
+    tx, toff, tlen, tnif, tsrc, cnt = F.build(buf, off, pl, tn, 128, z(128, np.uint8), z(4, np.uint32), z(4, np.uint16),
+                                              z(4, np.int8), z(4, np.uint32))
+    assert cnt.tolist() == [2, 0] and toff[:2].tolist() == [2, 66] and tlen[:2].tolist() == [59, 39]
+    assert bytes(tx[2:61]) == ipb[:59] and bytes(tx[66:105]) == ipb[20:59] and (tx[105:] == 0xEE).all()
+
+
 @pytest.mark.skipif(not os.access(P.APP, os.X_OK), reason="needs oracle/_ref/mos_app_emul (make -C oracle ref)")
 @pytest.mark.parametrize("name", sorted(P.SCENARIOS))
 def test_restatement_matches_mos(tmp_path, name):

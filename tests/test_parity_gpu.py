@@ -499,6 +499,23 @@ def test_bogus_offsets_after_sorted_frames(gpu_ctx):
             gpu_ctx.set_variant(2)
 
 
+def test_bogus_offsets_in_tiles_out_of_buffer_order(gpu_ctx):
+    """Descriptors in reverse buffer order with bogus entries in the last bytes of
+    the 32-bit range behind them: off + the header window wraps past 2^32, which
+    is no tail (the streamers of a tile out of buffer order once counted from the
+    wrapped split up to the offset, in steps that wrapped again: without end)."""
+    frames = [tcp_frame(payload=bytes(range(200)) * 7) for _ in range(70)]
+    buf, off, ln = pack_frames(frames)
+    off = np.concatenate([off[::-1], np.array([0xFFFFFFF0, 0xFFFFFFFF, 0xFFFFFFC0], np.uint32)])
+    ln = np.concatenate([ln[::-1], np.array([0, 0, 1500], np.uint16)])
+    for variant in STREAM_VARIANTS + [2]:
+        gpu_ctx.set_variant(variant)
+        try:
+            run_both(gpu_ctx, buf, off, ln, mosrx.default_params())
+        finally:
+            gpu_ctx.set_variant(2)
+
+
 @pytest.mark.parametrize("layout", ["frames_off_len", "off_len_frames", "gaps", "too_sparse", "overlap"])
 def test_host_one_block_layouts(gpu_ctx, layout):
     """classify_host with frames and descriptors in one block (the gpu_module
