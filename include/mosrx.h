@@ -548,6 +548,90 @@ typedef struct mosrx_queue_fwd {
 } mosrx_queue_fwd;
 int mosrx_queue_set_fwd(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd *f);
 
+/* The descriptor form of the ring build, for a host that still holds the
+ * received frames (the drop-in backend's staging, a pinned source ring): what
+ * it lacks per sent frame, 18 bytes, in place of the frame.  The sent rule and
+ * the entry order are the ring form's: ring q's r-th sent frame, in arrival
+ * order, has entry e = rings[q].start + r, and
+ *   d_tx_src[e]   u32   the frame's index in the batch
+ *   d_tx_len[e]   u16   its TX length
+ *   d_tx_mac[e]   12 bytes (three dwords, 4-byte aligned): h_dest then h_source,
+ *                 bytes 0 .. 11 of the frame mosrx_fwd_build_rings_dev writes --
+ *                 kind IP: a_haddr[arp_idx] (the frame's own h_dest when arp_idx
+ *                 is 0xFFFF, the nic_forward_table path) then
+ *                 netdev_haddr[out_ifidx]; kind ETH: the frame's own bytes
+ *   d_rings[q]    {start, count, dropped = 0, units}: start the sent frames of
+ *                 the netdevs below q, units the sum of ceil((2 + tx_len) / 16)
+ *                 over the ring's frames -- what a byte ring large enough to drop
+ *                 nothing reports, so a host can size one
+ * There is no capacity and nothing is dropped.  d_rings[0 .. nrings) is written
+ * whole by every call (n == 0 included: zeroes); entries at and past the total
+ * sent count and d_rings[nrings ..] are left untouched; the three entry arrays
+ * need room for n entries.  Three launches on one stream (the ring form's
+ * totals and scan, then a store launch); allocates nothing, graph-capturable.
+ * -EINVAL: NULL or misaligned pointer (d_rings, d_scratch to 16 bytes, d_tx_src /
+ * d_tx_mac to 4, d_tx_len to 2), nrings outside 1 .. MOSRX_FWD_MAX_NETDEVS or
+ * below the installed tables' num_netdevs, scratch under
+ * mosrx_fwd_desc_scratch_bytes(n, nrings); -ENOENT: no tables set.  A refused
+ * call launches nothing. */
+int    mosrx_fwd_desc_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint32_t nrings,
+                                uint32_t *d_tx_src, uint16_t *d_tx_len, uint32_t *d_tx_mac, mosrx_fwd_ring *d_rings,
+                                void *d_scratch, size_t scratch_bytes, void *stream);
+size_t mosrx_fwd_desc_scratch_bytes(uint32_t n, uint32_t nrings);
+
+/* The descriptor form attached to a batch queue: every mosrx_queue_run then
+ * enqueues the plan launch and the descriptor form's three over every batch,
+ * four launches whatever nb is; batch i's outputs are byte for byte those of
+ * mosrx_fwd_plan_dev + mosrx_fwd_desc_rings_dev on that batch alone.  Fields
+ * and rules as mosrx_queue_fwd's: d_plan[i] / d_tx_src[i] / d_tx_len[i] /
+ * d_tx_mac[i] may be NULL for an empty batch only, d_rings[i] is required for
+ * every batch; everything is validated before anything changes; f == NULL
+ * detaches.  A queue carries either this attachment or mosrx_queue_set_fwd's:
+ * attaching one while the other is attached is -EINVAL.  A run checks before it
+ * launches anything: -ENOENT with no tables installed, -EINVAL with nrings below
+ * the installed tables' num_netdevs; nothing is enqueued then. */
+typedef struct mosrx_queue_fwd_desc {
+	const uint8_t *in_ifidx;
+	mosrx_fwd *const *d_plan;
+	uint32_t  nrings;
+	uint32_t       *const *d_tx_src;
+	uint16_t       *const *d_tx_len;
+	uint32_t       *const *d_tx_mac;
+	mosrx_fwd_ring *const *d_rings;
+} mosrx_queue_fwd_desc;
+int mosrx_queue_set_fwd_desc(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd_desc *f);
+
+/* The same attached to the next group submit on `slot`, once, the way
+ * mosrx_slot_steer* arm it (and together with such an arm, or alone): the plan
+ * and descriptor launches follow the group's classify launch, and the steer
+ * launches if armed, on the slot's stream, with any
+ * mosrx_classify_host_group_submit* variant (16- or 8-byte records).  Batch i's
+ * outputs land in h_tx_src[i] / h_tx_len[i] / h_tx_mac[i] (n_i entries each; 4-,
+ * 2-, 4-byte aligned; may be NULL for an empty batch), h_rings[i][nrings]
+ * (required for every batch) and, when h_plan is given, h_plan[i] (8-byte
+ * aligned).  Placement follows the other outputs' rule: written in place for a
+ * direct group whose outputs, these included (h_rings 16-byte aligned), are all
+ * pinned -- then byte for byte mosrx_fwd_desc_rings_dev's -- otherwise copied
+ * back with the records: all n_i entries of each array are then overwritten,
+ * and those at and past the sent count hold nothing of meaning.  A group of
+ * empty batches gets its zeroed rings.  The pointer arrays must stay valid
+ * until the submit.  in_ifidx: nb input netdevs, NULL: all 0.  The slot's device
+ * buffers are part of mosrx_classify_host_reserve.  o == NULL disarms.
+ * -EBUSY while the slot runs; -ENOENT without tables and -EINVAL for nrings
+ * outside 1 .. MOSRX_FWD_MAX_NETDEVS or below num_netdevs or a NULL array, here
+ * and again at the submit (the tables in effect then), before anything is
+ * submitted. */
+typedef struct mosrx_slot_fwd_out {
+	const uint8_t *in_ifidx;
+	uint32_t  nrings;
+	mosrx_fwd      *const *h_plan;
+	uint32_t       *const *h_tx_src;
+	uint16_t       *const *h_tx_len;
+	uint32_t       *const *h_tx_mac;
+	mosrx_fwd_ring *const *h_rings;
+} mosrx_slot_fwd_out;
+int mosrx_slot_fwd(mosrx_ctx *c, int slot, const mosrx_slot_fwd_out *o);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned
@@ -718,7 +802,10 @@ enum { MOSRX_OP_CLASSIFY = 0, MOSRX_OP_CLASSIFY_FH = 1, MOSRX_OP_BPF = 2, MOSRX_
                           * what the batch's frames need at most */,
        MOSRX_OP_FWD_RINGS = 12 /* MOSRX_OP_FWD_PLAN followed by the ring build (-ENOTSUP from
                                 * mosrx_time_op_dispatch); outputs and scratch are the timing call's own, ring_cap
-                                * what the batch's frames need at most, nrings the tables' num_netdevs */ };
+                                * what the batch's frames need at most, nrings the tables' num_netdevs */,
+       MOSRX_OP_FWD_DESC = 13 /* MOSRX_OP_FWD_PLAN followed by the descriptor form of the ring build (-ENOTSUP from
+                               * mosrx_time_op_dispatch); outputs and scratch are the timing call's own, nrings the
+                               * tables' num_netdevs */ };
 int  mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t nb, void *const *out,
                    void *const *aux, uint32_t iters, uint32_t nstreams, float *total_ms, float *avg_kernel_ms);
 /* The kernel's own duration, averaged over `iters` back-to-back launches on

@@ -119,6 +119,28 @@ typedef struct mosrx_queue_side {
 	const uint32_t *match;       /* n BPF match masks, NULL where MOSRX_PKT_RX_MATCH has none */
 	const mosrx_tcpinfo *tcpinfo; /* n pkt_info records, NULL where MOSRX_PKT_RX_TCPINFO has none */
 } mosrx_queue_side;
+#define MOSRX_PKT_RX_FWD     0x1C   /* argp: mosrx_fwd_view * -- the exposed batch's forwarding plan and
+                                     * descriptor rings (mosrx_gpu_module_set_fwd; -1 without it) */
+/* The pointers go into the batch's own pinned host arrays and are valid until
+ * the next recv_pkts on the netdev.  Ring q's entries are rings[q].start ..
+ * rings[q].start + rings[q].count of tx_src / tx_len / tx_mac (mosrx_fwd_desc_rings_dev);
+ * entries at and past the rings' total count hold nothing of meaning (a group
+ * whose outputs were copied back has them overwritten).  -1: forwarding is
+ * off, no batch is exposed, the batch's launch did not fill the outputs, or
+ * MOSRX_PKT_RX_RECLASSIFY / MOSRX_PKT_SET_PARAMS has touched the exposed batch
+ * (the plan depends on forward, num_msp and the records): the caller falls
+ * back to its per-frame path (mosrx_forward_frame) for that batch.  At a hub
+ * endpoint always -1: forwarding behind the hub is not built. */
+typedef struct mosrx_fwd_view {
+	uint32_t n, nrings;
+	const uint8_t  *frames;      /* frame i of the batch is frames + off[i] */
+	const uint32_t *off;
+	const mosrx_fwd *plan;       /* n */
+	const uint32_t *tx_src;
+	const uint16_t *tx_len;
+	const uint32_t *tx_mac;      /* 3 dwords an entry */
+	const mosrx_fwd_ring *rings; /* nrings */
+} mosrx_fwd_view;
 typedef struct mosrx_rx_state {
 	uint32_t num_msp, num_esp;   /* the stack state of the batch's verdicts */
 	uint32_t gen;                /* the netdev's parameter / filter generation they were made with */
@@ -530,6 +552,36 @@ typedef struct mosrx_fwd_send_stats { uint64_t sent, no_buffer, send_calls; } mo
 int mosrx_fwd_rings_send(const io_module_func *iom, struct mtcp_thread_context *ctx,
                          const uint8_t *h_tx_frames, const uint32_t *h_tx_off, const uint16_t *h_tx_len,
                          const mosrx_fwd_ring *h_rings, uint32_t nrings, mosrx_fwd_send_stats *st);
+/* The same hand-over from host copies of mosrx_fwd_desc_rings_dev's outputs and
+ * the received batch itself (`frames`, `off`: the batch the plan was made
+ * from): per entry get_wptr(ctx, q, len), a memcpy of len bytes from
+ * frames + off[tx_src[e]], then the 12 bytes of tx_mac[e] over the start.
+ * Frame for frame and byte for byte what mosrx_fwd_rings_send sends from the
+ * byte rings of the same plan; the same calls, counts and refusals.  The
+ * descriptors are trusted as the byte rings' tx_off is: tx_src[e] indexes off[]
+ * and tx_len[e] bytes are read at off[tx_src[e]] with no bound of the batch
+ * (the signature carries none); a caller that cannot trust them checks
+ * tx_src[e] < n and off + tx_len <= frames_bytes first. */
+/* Forward the batch exposed on `ifidx` of a gpu_module_func context: the
+ * MOSRX_PKT_RX_FWD ioctl, then mosrx_fwd_desc_send of its view to the same
+ * module.  Returns the ioctl's -1 untouched (the caller then forwards that batch
+ * per frame), -EIO for a view whose entries do not lie in the batch, else
+ * mosrx_fwd_desc_send's return.  Once per batch, after the caller's walk and
+ * before the next recv_pkts. */
+int mosrx_backend_forward(const io_module_func *iom, struct mtcp_thread_context *ctx, int ifidx,
+                          mosrx_fwd_send_stats *st);
+/* Forwarding on gpu_module_func: a setting of the module like
+ * mosrx_gpu_module_set_steer_one, made before init_handle.  Each context opened
+ * then gets mosrx_fwd_set(t) and mosrx_fwd_set_listener(listener), its groups'
+ * pinned forwarding outputs are allocated with the others, and every group
+ * submit is armed (mosrx_slot_fwd) with in_ifidx = the netdev; a lone batch
+ * takes the group path.  NULL turns forwarding off (the default).  -EINVAL for
+ * tables mosrx_fwd_set refuses: the setting stays as it was. */
+int mosrx_gpu_module_set_fwd(const mosrx_fwd_tables *t, int listener);
+int mosrx_fwd_desc_send(const io_module_func *iom, struct mtcp_thread_context *ctx, const uint8_t *frames,
+                        const uint32_t *off, const uint32_t *h_tx_src, const uint16_t *h_tx_len,
+                        const uint32_t *h_tx_mac, const mosrx_fwd_ring *h_rings, uint32_t nrings,
+                        mosrx_fwd_send_stats *st);
 
 /* ---- residency of frames from a paced source (latency of the drop-in path) ----
  * mosrx_source_paced: `inner`'s frames released at `rate_pps` -- frame k

@@ -82,6 +82,11 @@ struct stage {
 	uint32_t *qfh, *qmt;      /* pinned, the gather's side arrays (cfg.steer = 3): fh / match in the order of sidx */
 	mosrx_tcpinfo *qti;       /*   and ti; each NULL when its last launch did not gather it (MOSRX_PKT_RX_QUEUE_SIDE) */
 	int sided;                /* its last launch was armed with them */
+	mosrx_fwd *fplan;         /* pinned, forwarding (mosrx_gpu_module_set_fwd): n plan records, */
+	uint32_t *ftsrc, *ftmac;  /*   the descriptor rings' entries (n; 3 dwords each), */
+	uint16_t *ftlen;
+	mosrx_fwd_ring *frings;   /*   and the ring rows */
+	int fwd;                  /* its last launch filled them and nothing has touched the batch since (MOSRX_PKT_RX_FWD) */
 	uint32_t n, max_len;
 	uint32_t rec0;            /* its first record's index in the group's record arrays */
 	uint32_t stride;          /* frame i at off[0] + i * stride (a fixed-size packing), else 0: the layout hint */
@@ -113,6 +118,10 @@ struct group {
 	uint16_t *sqlen;          /*   and lengths */
 	uint32_t *sqfh, *sqmt;    /* cfg.steer = 3: rec_cap gathered flow hashes / match masks, */
 	mosrx_tcpinfo *sqti;      /*   and pkt_info; each only with the array it follows (fh, match, ti) */
+	mosrx_fwd *fplan;         /* forwarding set: rec_cap plan records, */
+	uint32_t *ftsrc, *ftmac;  /*   rec_cap entries of the descriptor rings, */
+	uint16_t *ftlen;
+	mosrx_fwd_ring *frings;   /*   cap_st x MOSRX_FWD_MAX_NETDEVS ring rows */
 	uint64_t rec_cap;         /* frames the record arrays hold */
 	struct stage *st;         /* cap_st stages */
 	uint32_t cap_st;
@@ -207,6 +216,35 @@ int mosrx_gpu_module_set_steer_one(int32_t max_frames)
 }
 
 int32_t mosrx_gpu_module_get_steer_one(void) { return g_steer_one; }
+
+/* mosrx_gpu_module_set_fwd: the tables every context opened from now on gets,
+ * and whether an end-host socket listens; g_fwd_on 0: forwarding off */
+static mosrx_fwd_tables g_fwd;
+static int g_fwd_on, g_fwd_listener;
+#define FWD_NRINGS (g_fwd.num_netdevs ? g_fwd.num_netdevs : 1u)
+
+int mosrx_gpu_module_set_fwd(const mosrx_fwd_tables *t, int listener)
+{
+	uint32_t i;
+	if (t) {   /* mosrx_fwd_set's own rules: a refused setting leaves the one in place */
+		if (t->num_routes > MOSRX_FWD_MAX_ROUTES || t->num_arp > MOSRX_FWD_MAX_ARP ||
+		    t->num_netdevs > MOSRX_FWD_MAX_NETDEVS)
+			return -EINVAL;
+		for (i = 0; i < t->num_routes; i++)
+			if (t->routes[i].nif < 0 || (uint32_t)t->routes[i].nif >= t->num_netdevs)
+				return -EINVAL;
+		for (i = 0; t->has_nic_fwd && i < MOSRX_FWD_MAX_NETDEVS; i++)
+			if (t->nic_fwd[i] != -1 && (t->nic_fwd[i] < 0 || (uint32_t)t->nic_fwd[i] >= t->num_netdevs))
+				return -EINVAL;
+	}
+	pthread_mutex_lock(&g_lock);
+	if (t)
+		g_fwd = *t;
+	g_fwd_on = t != NULL;
+	g_fwd_listener = t && listener;
+	pthread_mutex_unlock(&g_lock);
+	return 0;
+}
 
 int mosrx_gpu_module_get_cfg(mosrx_gpu_module_cfg *cfg)
 {
@@ -459,6 +497,11 @@ static void group_free(mosrx_ctx *mc, struct group *g)
 	if (g->sqfh) mosrx_host_free(mc, g->sqfh);
 	if (g->sqmt) mosrx_host_free(mc, g->sqmt);
 	if (g->sqti) mosrx_host_free(mc, g->sqti);
+	if (g->fplan) mosrx_host_free(mc, g->fplan);
+	if (g->ftsrc) mosrx_host_free(mc, g->ftsrc);
+	if (g->ftlen) mosrx_host_free(mc, g->ftlen);
+	if (g->ftmac) mosrx_host_free(mc, g->ftmac);
+	if (g->frings) mosrx_host_free(mc, g->frings);
 	free(g->st);
 	memset(g, 0, sizeof(*g));
 }
@@ -537,7 +580,13 @@ static int group_alloc_sized(mosrx_ctx *mc, struct group *g, uint64_t bytes)
 	    (g_cfg.steer == 3 &&
 	     ((g_cfg.flowhash && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sqfh)) ||
 	      (MATCH_UP_FRONT && mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->sqmt)) ||
-	      (g_cfg.tcpinfo && mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_tcpinfo), (void **)&g->sqti)))))
+	      (g_cfg.tcpinfo && mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_tcpinfo), (void **)&g->sqti)))) ||
+	    (g_fwd_on && (mosrx_host_alloc(mc, g->rec_cap * sizeof(mosrx_fwd), (void **)&g->fplan) ||
+	                  mosrx_host_alloc(mc, g->rec_cap * 4, (void **)&g->ftsrc) ||
+	                  mosrx_host_alloc(mc, g->rec_cap * 2, (void **)&g->ftlen) ||
+	                  mosrx_host_alloc(mc, g->rec_cap * 12, (void **)&g->ftmac) ||
+	                  mosrx_host_alloc(mc, (size_t)g->cap_st * MOSRX_FWD_MAX_NETDEVS * sizeof(mosrx_fwd_ring),
+	                                   (void **)&g->frings))))
 		return -ENOMEM;
 	return 0;
 }
@@ -621,6 +670,11 @@ static void gpu_init_handle(struct mtcp_thread_context *ctx)
 		 * by one launch (left at 0 the context is not touched: off is its default) */
 		if (g_steer_one && (rc = mosrx_set_steer_one(is->mc, (uint32_t)g_steer_one))) {
 			fprintf(stderr, "[mosrx] gpu_module: steer_one %d: %s\n", g_steer_one, mosrx_strerror(rc));
+			exit(EXIT_FAILURE);
+		}
+		/* mosrx_gpu_module_set_fwd: the context's tables; every group submit is then armed */
+		if (g_fwd_on && ((rc = mosrx_fwd_set(is->mc, &g_fwd)) || (rc = mosrx_fwd_set_listener(is->mc, g_fwd_listener)))) {
+			fprintf(stderr, "[mosrx] gpu_module: mosrx_fwd_set: %s\n", mosrx_strerror(rc));
 			exit(EXIT_FAILURE);
 		}
 		is->src = (cpu < MAX_THREADS && g_src_cpu[cpu][i]) ? g_src_cpu[cpu][i] : g_cfg.src[i];
@@ -787,6 +841,12 @@ static void group_fill(struct if_state *is, struct group *g)
 		s->qoff = g->sqoff ? g->sqoff + recs : NULL;
 		s->qlen = g->sqlen ? g->sqlen + recs : NULL;
 		s->gathered = s->sided = 0;
+		s->fplan = g->fplan ? g->fplan + recs : NULL;
+		s->ftsrc = g->ftsrc ? g->ftsrc + recs : NULL;
+		s->ftlen = g->ftlen ? g->ftlen + recs : NULL;
+		s->ftmac = g->ftmac ? g->ftmac + 3 * recs : NULL;
+		s->frings = g->frings ? g->frings + (size_t)i * MOSRX_FWD_MAX_NETDEVS : NULL;
+		s->fwd = 0;
 		if (!s->n)
 			break;
 		g->nst++;
@@ -869,6 +929,13 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	uint16_t *gl[MOSRX_MAX_GROUP];
 	uint32_t *gf[MOSRX_MAX_GROUP], *gm[MOSRX_MAX_GROUP];
 	mosrx_tcpinfo *gt[MOSRX_MAX_GROUP];
+	/* forwarding set: every group is armed with the plan and the descriptor rings, in_ifidx this netdev */
+	mosrx_fwd *fp[MOSRX_MAX_GROUP];
+	uint32_t *fs[MOSRX_MAX_GROUP], *fm[MOSRX_MAX_GROUP];
+	uint16_t *fl[MOSRX_MAX_GROUP];
+	mosrx_fwd_ring *fr[MOSRX_MAX_GROUP];
+	uint8_t fi[MOSRX_MAX_GROUP];
+	const int fwd = g_fwd_on && g->fplan && g->frings;
 	const int gather = g_cfg.steer >= 2 && g->sqrec;
 	/* cfg.steer = 3: the side arrays this submit makes are gathered with the records */
 	const int side = gather && g_cfg.steer == 3;
@@ -902,6 +969,13 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 		gm[i - first] = s->qmt = side_mt ? g->sqmt + s->rec0 : NULL;
 		gt[i - first] = s->qti = side_ti ? g->sqti + s->rec0 : NULL;
 		s->sided = s->gathered && side;
+		fp[i - first] = s->fplan;
+		fs[i - first] = s->ftsrc;
+		fl[i - first] = s->ftlen;
+		fm[i - first] = s->ftmac;
+		fr[i - first] = s->frings;
+		fi[i - first] = (uint8_t)(is - pv->ifs);
+		s->fwd = fwd;
 		s->msp = is->params.num_msp;
 		s->esp = is->params.num_esp;
 		s->gen = is->gen;
@@ -917,6 +991,14 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	                    : gather ? mosrx_slot_steer_gather(is->mc, k, sx, sq, gr, go, gl)
 	                             : mosrx_slot_steer(is->mc, k, sx, sq)))
 		return -1;
+	if (fwd) {
+		const mosrx_slot_fwd_out fo = {fi, FWD_NRINGS, fp, fs, fl, fm, fr};
+		if (mosrx_slot_fwd(is->mc, k, &fo)) {
+			if (g_cfg.steer)
+				mosrx_slot_steer(is->mc, k, NULL, NULL);
+			return -1;
+		}
+	}
 	if (compact && is->nprog)   /* 8-byte records + the set's masks: the fused kernel's 8-byte form */
 		rc = mosrx_classify_host_group_submit_bpf_c8(is->mc, k, b, nb, out8, g_cfg.flowhash ? fh : NULL, mt);
 	else if (compact)
@@ -927,13 +1009,15 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	 * the kernel takes the batch as arguments); with cfg.direct_kb a lone batch
 	 * takes the group path, which can run it with no copies (and with cfg.steer,
 	 * since the group submits are the steered ones) */
-	else if (nb == 1 && !g_cfg.flowhash && !g_cfg.direct_kb && !g_cfg.steer)
+	else if (nb == 1 && !g_cfg.flowhash && !g_cfg.direct_kb && !g_cfg.steer && !fwd)
 		rc = mosrx_classify_host_submit_ex(is->mc, k, &b[0], out[0], ti[0]);
 	else
 		rc = mosrx_classify_host_group_submit_ex(is->mc, k, b, nb, out, g_cfg.tcpinfo ? ti : NULL,
 		                                         g_cfg.flowhash ? fh : NULL);
 	if (rc && g_cfg.steer)   /* a submit refused before it took the arm: sx / sq end with this call */
 		mosrx_slot_steer(is->mc, k, NULL, NULL);
+	if (rc && fwd)
+		mosrx_slot_fwd(is->mc, k, NULL);
 	return rc;
 }
 
@@ -1326,6 +1410,21 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 		v->tcpinfo = s->has_ti && s->qti ? s->qti + q0 : NULL;
 		return 0;
 	}
+	case MOSRX_PKT_RX_FWD: {
+		mosrx_fwd_view *v = argp;
+		if (!g_fwd_on || !s || !s->fwd)
+			return -1;
+		v->n = s->n;
+		v->nrings = FWD_NRINGS;
+		v->frames = s->frames;
+		v->off = s->off;
+		v->plan = s->fplan;
+		v->tx_src = s->ftsrc;
+		v->tx_len = s->ftlen;
+		v->tx_mac = s->ftmac;
+		v->rings = s->frings;
+		return 0;
+	}
 	case MOSRX_PKT_RX_TCPINFO:
 		if (!s || !s->has_ti)
 			return -1;
@@ -1340,6 +1439,10 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 			return -1;
 		pv->ifs[nif].params = *(const mosrx_params *)argp;
 		pv->ifs[nif].gen++;
+		/* the exposed batch's plan was made under the old forward / num_msp: the
+		 * caller falls back to its per-frame path for it (MOSRX_PKT_RX_FWD is -1) */
+		if (s)
+			pv->ifs[nif].g[pv->ifs[nif].cur].st[pv->ifs[nif].cur_idx].fwd = 0;
 		return 0;
 	case MOSRX_PKT_SET_BPF:
 		return set_bpf(pv, &pv->ifs[nif], (const mosrx_bpf_set_arg *)argp);
@@ -1357,9 +1460,15 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 	}
 	case MOSRX_PKT_RX_RECLASSIFY: {
 		struct if_state *is = &pv->ifs[nif];
+		int rc;
 		if (!s)
 			return -1;
-		return group_reclassify(pv, is, is->cur, is->cur_idx) ? -1 : 0;
+		rc = group_reclassify(pv, is, is->cur, is->cur_idx) ? -1 : 0;
+		/* the exposed batch was touched: its forwarding view is withdrawn (the
+		 * caller's per-frame path serves it); the group's later batches keep
+		 * the plans this launch made for them */
+		is->g[is->cur].st[is->cur_idx].fwd = 0;
+		return rc;
 	}
 	case DRV_NAME:
 		*(const char **)argp = "mosrx_gpu";

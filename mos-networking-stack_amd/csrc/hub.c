@@ -247,6 +247,8 @@ static int32_t hub_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 			return -1;
 		*(mosrx_queue_side *)argp = s->side;
 		return 0;
+	case MOSRX_PKT_RX_FWD:       /* forwarding behind the hub is not built: an endpoint has no view */
+		return -1;
 	default:
 		return -1;
 	}

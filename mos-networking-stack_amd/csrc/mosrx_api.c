@@ -210,6 +210,14 @@ int mosrx_open(int device, const mosrx_params *p, mosrx_ctx **out)
 		    hipMalloc((void **)&c->slot[i].d_xdesc, MOSRX_MAX_GROUP * sizeof(mosrx_xdesc)) != hipSuccess ||
 		    hipHostMalloc((void **)&c->slot[i].h_xdesc, MOSRX_MAX_GROUP * sizeof(mosrx_xdesc),
 		                  hipHostMallocDefault) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_fdesc, MOSRX_MAX_GROUP * sizeof(mosrx_fdesc)) != hipSuccess ||
+		    hipHostMalloc((void **)&c->slot[i].h_fdesc, MOSRX_MAX_GROUP * sizeof(mosrx_fdesc),
+		                  hipHostMallocDefault) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_ddesc, MOSRX_MAX_GROUP * sizeof(mosrx_ddesc)) != hipSuccess ||
+		    hipHostMalloc((void **)&c->slot[i].h_ddesc, MOSRX_MAX_GROUP * sizeof(mosrx_ddesc),
+		                  hipHostMallocDefault) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_frings,
+		              (size_t)MOSRX_MAX_GROUP * MOSRX_FWD_MAX_NETDEVS * sizeof(mosrx_fwd_ring)) != hipSuccess ||
 		    hipMalloc((void **)&c->slot[i].d_cnt, MOSRX_CNT_WORDS * 4) != hipSuccess ||
 		    hipHostMalloc((void **)&c->slot[i].h_cnt, MOSRX_CNT_WORDS * 4, hipHostMallocDefault) != hipSuccess ||
 		    !(c->slot[i].h_prev = calloc(MOSRX_CNT_WORDS, 4))) {
@@ -248,6 +256,12 @@ static void slot_free(struct slot *s)
 	if (s->d_sqfh) hipFree(s->d_sqfh);
 	if (s->d_sqmt) hipFree(s->d_sqmt);
 	if (s->d_sqti) hipFree(s->d_sqti);
+	if (s->d_fplan) hipFree(s->d_fplan);
+	if (s->d_ftsrc) hipFree(s->d_ftsrc);
+	if (s->d_ftlen) hipFree(s->d_ftlen);
+	if (s->d_ftmac) hipFree(s->d_ftmac);
+	if (s->d_fscr) hipFree(s->d_fscr);
+	s->d_fplan = NULL; s->d_ftsrc = NULL; s->d_ftlen = NULL; s->d_ftmac = NULL; s->d_fscr = NULL;
 	s->d_sqfh = NULL; s->d_sqmt = NULL; s->d_sqti = NULL;
 	s->d_sidx = NULL; s->d_shist = NULL;
 	s->d_sqrec = NULL; s->d_sqoff = NULL; s->d_sqlen = NULL;
@@ -288,6 +302,11 @@ void mosrx_close(mosrx_ctx *c)
 		if (c->slot[i].h_gdesc) hipHostFree(c->slot[i].h_gdesc);
 		if (c->slot[i].d_xdesc) hipFree(c->slot[i].d_xdesc);
 		if (c->slot[i].h_xdesc) hipHostFree(c->slot[i].h_xdesc);
+		if (c->slot[i].d_fdesc) hipFree(c->slot[i].d_fdesc);
+		if (c->slot[i].h_fdesc) hipHostFree(c->slot[i].h_fdesc);
+		if (c->slot[i].d_ddesc) hipFree(c->slot[i].d_ddesc);
+		if (c->slot[i].h_ddesc) hipHostFree(c->slot[i].h_ddesc);
+		if (c->slot[i].d_frings) hipFree(c->slot[i].d_frings);
 		if (c->slot[i].d_cnt) hipFree(c->slot[i].d_cnt);
 		if (c->slot[i].h_cnt) hipHostFree(c->slot[i].h_cnt);
 		free(c->slot[i].h_prev);
@@ -649,6 +668,13 @@ static size_t steer_group_scratch(uint32_t n)
 	return ((size_t)n / MOSRX_STEER_TILE + MOSRX_MAX_GROUP + 1) * MOSRX_STEER_BINS * 4;
 }
 
+/* Scratch rows of MOSRX_FWD_ROW bytes an armed group of n frames can need
+ * (mosrx_slot_fwd): a row per ring and tile, the tile counts rounded up per batch. */
+static size_t fwd_group_scratch(uint32_t n)
+{
+	return ((size_t)n / MOSRX_FWD_TILE + MOSRX_MAX_GROUP + 1) * MOSRX_FWD_MAX_NETDEVS * MOSRX_FWD_ROW;
+}
+
 int mosrx__slot_reserve(mosrx_ctx *c, struct slot *s, uint64_t frames_bytes, uint32_t n)
 {
 	if (frames_bytes > s->cap_frames || n > s->cap_n) {
@@ -671,7 +697,12 @@ int mosrx__slot_reserve(mosrx_ctx *c, struct slot *s, uint64_t frames_bytes, uin
 		    hipMalloc((void **)&s->d_sqlen, (size_t)nn * 2) != hipSuccess ||
 		    hipMalloc((void **)&s->d_sqfh, (size_t)nn * 4) != hipSuccess ||
 		    hipMalloc((void **)&s->d_sqmt, (size_t)nn * 4) != hipSuccess ||
-		    hipMalloc((void **)&s->d_sqti, (size_t)nn * sizeof(mosrx_tcpinfo)) != hipSuccess) {
+		    hipMalloc((void **)&s->d_sqti, (size_t)nn * sizeof(mosrx_tcpinfo)) != hipSuccess ||
+		    hipMalloc((void **)&s->d_fplan, (size_t)nn * sizeof(mosrx_fwd)) != hipSuccess ||
+		    hipMalloc((void **)&s->d_ftsrc, (size_t)nn * 4) != hipSuccess ||
+		    hipMalloc((void **)&s->d_ftlen, (size_t)nn * 2) != hipSuccess ||
+		    hipMalloc((void **)&s->d_ftmac, (size_t)nn * 12) != hipSuccess ||
+		    hipMalloc((void **)&s->d_fscr, fwd_group_scratch(nn)) != hipSuccess) {
 			slot_free(s);
 			return -ENOMEM;
 		}
@@ -1233,6 +1264,136 @@ static int group_steer(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint3
 	return 0;
 }
 
+/* The device addresses of an armed group's forwarding outputs (mosrx_slot_fwd),
+ * when every one of them is pinned and aligned to its stores: into the slot's
+ * two forwarding tables. */
+static int fwd_outputs(int device, const mosrx_batch *b, uint32_t nb, const mosrx_slot_fwd_out *o, mosrx_fdesc *fd,
+                       mosrx_ddesc *dd)
+{
+	uint32_t i;
+	for (i = 0; i < nb; i++) {
+		const uint64_t n = b[i].n;
+		if (((uintptr_t)o->h_rings[i] & 15) ||
+		    !(dd[i].rings = mosrx__host_dev_of(o->h_rings[i], (uint64_t)o->nrings * sizeof(mosrx_fwd_ring), device)))
+			return 0;
+		fd[i].rings = dd[i].rings;
+		if (!n)
+			continue;
+		fd[i].plan = NULL;   /* (no h_plan: the slot's own array) */
+		if (o->h_plan && (((uintptr_t)o->h_plan[i] & 7) ||
+		                  !(fd[i].plan = mosrx__host_dev_of(o->h_plan[i], n * sizeof(mosrx_fwd), device))))
+			return 0;
+		if (!(dd[i].tx_src = mosrx__host_dev_of(o->h_tx_src[i], n * 4, device)) ||
+		    !(dd[i].tx_len = mosrx__host_dev_of(o->h_tx_len[i], n * 2, device)) ||
+		    !(dd[i].tx_mac = mosrx__host_dev_of(o->h_tx_mac[i], n * 12, device)))
+			return 0;
+	}
+	return 1;
+}
+
+static void fwd_mark_used(mosrx_ctx *c);
+
+/* The plan and descriptor launches of an armed group, behind its classify (and
+ * steer) launches on the slot's stream: over the records and descriptors where
+ * the classify launch wrote and read them (s->h_qdesc), into the caller's
+ * pinned arrays (in_place: fwd_outputs filled the tables) or the slot's
+ * buffers, which are then copied back per batch -- all n entries of each array:
+ * those at and past the sent count then hold nothing of meaning. */
+static int group_fwd(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
+                     const mosrx_slot_fwd_out *o)
+{
+	mosrx_fqparams fq;
+	mosrx_dqparams dq;
+	uint32_t i, tiles = 0;
+	uint64_t pre = 0;
+	int rc;
+	for (i = 0; i < nb; pre += b[i].n, i++) {
+		mosrx_fdesc *f = &s->h_fdesc[i];
+		mosrx_ddesc *d = &s->h_ddesc[i];
+		const mosrx_qdesc *q = &s->h_qdesc[i];
+		if (!in_place) {
+			f->plan = NULL;
+			d->rings = s->d_frings + (size_t)i * MOSRX_FWD_MAX_NETDEVS;
+			d->tx_src = b[i].n ? s->d_ftsrc + pre : NULL;
+			d->tx_len = b[i].n ? s->d_ftlen + pre : NULL;
+			d->tx_mac = b[i].n ? s->d_ftmac + 3 * pre : NULL;
+		}
+		if (!f->plan || !b[i].n)
+			f->plan = b[i].n ? s->d_fplan + pre : NULL;
+		f->rings = d->rings;
+		f->tx = NULL;
+		f->tx_off = NULL;
+		f->tx_len = NULL;
+		f->tx_src = NULL;
+		f->frames = d->frames = q->frames;
+		f->off = d->off = q->off;
+		f->len = q->len;
+		f->rec = (const uint8_t *)q->out;
+		d->plan = f->plan;
+		f->frames_bytes = d->frames_bytes = q->frames_bytes;
+		f->n = d->n = b[i].n;
+		f->in_ifidx = o->in_ifidx ? o->in_ifidx[i] : 0;
+		f->tile_base = d->tile_base = tiles;
+		d->pad = 0;
+		tiles += (b[i].n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+	}
+	HIPCHK(hipMemcpyAsync(s->d_fdesc, s->h_fdesc, nb * sizeof(mosrx_fdesc), hipMemcpyHostToDevice, s->stream));
+	HIPCHK(hipMemcpyAsync(s->d_ddesc, s->h_ddesc, nb * sizeof(mosrx_ddesc), hipMemcpyHostToDevice, s->stream));
+	memset(&fq, 0, sizeof(fq));
+	memset(&dq, 0, sizeof(dq));
+	fq.desc = s->d_fdesc;
+	fq.tab = dq.tab = c->d_fwd;
+	fq.scratch = dq.scratch = s->d_fscr;
+	fq.nb = dq.nb = nb;
+	fq.total_tiles = dq.total_tiles = tiles;
+	fq.rec_bytes = (uint32_t)rsz;
+	fq.forward = c->params.forward;
+	fq.num_msp = c->params.num_msp;
+	fq.listener = c->fwd_listener;
+	fq.nrings = dq.nrings = o->nrings;
+	dq.desc = s->d_ddesc;
+	fwd_mark_used(c);
+	if ((rc = mosrx_launch_fwd_desc_queue(&fq, &dq, (void *)s->stream)))
+		return rc;
+	for (i = 0, pre = 0; i < nb; pre += b[i].n, i++) {
+		const size_t n = b[i].n;
+		if (o->h_plan && n && s->h_fdesc[i].plan == s->d_fplan + pre)
+			HIPCHK(hipMemcpyAsync(o->h_plan[i], s->d_fplan + pre, n * sizeof(mosrx_fwd), hipMemcpyDeviceToHost, s->stream));
+		if (in_place)
+			continue;
+		HIPCHK(hipMemcpyAsync(o->h_rings[i], s->d_frings + (size_t)i * MOSRX_FWD_MAX_NETDEVS,
+		                      (size_t)o->nrings * sizeof(mosrx_fwd_ring), hipMemcpyDeviceToHost, s->stream));
+		if (!n)
+			continue;
+		HIPCHK(hipMemcpyAsync(o->h_tx_src[i], s->d_ftsrc + pre, n * 4, hipMemcpyDeviceToHost, s->stream));
+		HIPCHK(hipMemcpyAsync(o->h_tx_len[i], s->d_ftlen + pre, n * 2, hipMemcpyDeviceToHost, s->stream));
+		HIPCHK(hipMemcpyAsync(o->h_tx_mac[i], s->d_ftmac + 3 * pre, n * 12, hipMemcpyDeviceToHost, s->stream));
+	}
+	return 0;
+}
+
+int mosrx_slot_fwd(mosrx_ctx *c, int slot, const mosrx_slot_fwd_out *o)
+{
+	if (!c || slot < 0 || slot >= NSLOT)
+		return -EINVAL;
+	if (c->slot[slot].busy)
+		return -EBUSY;
+	if (!o) {
+		c->slot[slot].fwd_armed = 0;
+		return 0;
+	}
+	if (!o->h_tx_src || !o->h_tx_len || !o->h_tx_mac || !o->h_rings || o->nrings < 1 ||
+	    o->nrings > MOSRX_FWD_MAX_NETDEVS)
+		return -EINVAL;
+	if (!c->d_fwd)
+		return -ENOENT;
+	if (o->nrings < c->fwd_num_netdevs)
+		return -EINVAL;
+	c->slot[slot].fwd = *o;
+	c->slot[slot].fwd_armed = 1;
+	return 0;
+}
+
 int mosrx_classify_host_group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t nb,
                                      mosrx_result *const *h_out, mosrx_tcpinfo *const *h_tcpinfo)
 {
@@ -1260,6 +1421,8 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	uint32_t *const *h_sidx, *const *h_sqs;
 	struct gather_out go;
 	const uint32_t *msrc[MOSRX_MAX_GROUP];
+	mosrx_slot_fwd_out fo;
+	int fwd;
 	if (!c || slot < 0 || slot >= NSLOT || !b || !h_out || nb == 0 || nb > MOSRX_MAX_GROUP ||
 	    (h_match && h_tcpinfo) || (compact && h_tcpinfo))
 		return -EINVAL;
@@ -1278,9 +1441,24 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	s->steer_qrec = NULL;
 	s->steer_qoff = NULL;
 	s->steer_qlen = NULL;
+	/* ... and mosrx_slot_fwd: the tables may have changed since the arm */
+	fwd = s->fwd_armed;
+	fo = s->fwd;
+	s->fwd_armed = 0;
+	if (fwd && !c->d_fwd)
+		return -ENOENT;
+	if (fwd && fo.nrings < c->fwd_num_netdevs)
+		return -EINVAL;
 	for (i = 0; i < nb; i++) {
 		if ((rc = mosrx__check_batch(&b[i], 0)))
 			return rc;
+		if (fwd && (!fo.h_rings[i] || ((uintptr_t)fo.h_rings[i] & 3) ||
+		            (fo.in_ifidx && fo.in_ifidx[i] >= MOSRX_FWD_MAX_NETDEVS) ||
+		            (b[i].n && (!fo.h_tx_src[i] || !fo.h_tx_len[i] || !fo.h_tx_mac[i] ||
+		                        (((uintptr_t)fo.h_tx_src[i] | (uintptr_t)fo.h_tx_mac[i]) & 3) ||
+		                        ((uintptr_t)fo.h_tx_len[i] & 1) ||
+		                        (fo.h_plan && (!fo.h_plan[i] || ((uintptr_t)fo.h_plan[i] & 7)))))))
+			return -EINVAL;
 		if (b[i].n && (!h_out[i] || (h_tcpinfo && !h_tcpinfo[i]) || (h_fhash && !h_fhash[i]) ||
 		               (h_match && !h_match[i]) ||
 		               (h_sidx && (!h_sidx[i] || !h_sqs[i] || (((uintptr_t)h_sidx[i] | (uintptr_t)h_sqs[i]) & 3))) ||
@@ -1305,6 +1483,8 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 		                          mosrx__host_range_of(b[i].len, (uint64_t)b[i].n * 2)};
 	}
 	if (ntot == 0) {
+		for (i = 0; fwd && i < nb; i++)   /* n == 0: the zeroed rings only */
+			memset(fo.h_rings[i], 0, (size_t)fo.nrings * sizeof(mosrx_fwd_ring));
 		s->busy = 2;
 		s->direct = 0;
 		return 0;
@@ -1314,14 +1494,15 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	out_direct = direct && direct_outputs(c->device, b, nb, h_out, rsz, h_tcpinfo, h_fhash, h_match, od) &&
 	             (!h_sidx || steer_outputs(c->device, b, nb, h_sidx, h_sqs, s->h_sdesc)) &&
 	             (!go.qrec || gather_outputs(c->device, b, nb, rsz, &go, s->h_gdesc)) &&
-	             (!GATHER_SIDE(&go) || side_outputs(c->device, b, nb, &go, s->h_xdesc));
+	             (!GATHER_SIDE(&go) || side_outputs(c->device, b, nb, &go, s->h_xdesc)) &&
+	             (!fwd || fwd_outputs(c->device, b, nb, &fo, s->h_fdesc, s->h_ddesc));
 	if (!direct) {
 		group_copy(s, r, nr, &dev_bytes, 0);
 		if ((rc = mosrx__slot_reserve(c, s, dev_bytes, ntot)))
 			return rc;
 		if ((rc = group_copy(s, r, nr, &dev_bytes, 1)))
 			return rc;
-	} else if ((!out_direct || h_sidx) && (rc = mosrx__slot_reserve(c, s, 0, ntot))) {
+	} else if ((!out_direct || h_sidx || fwd) && (rc = mosrx__slot_reserve(c, s, 0, ntot))) {
 		return rc;   /* (a steered group's histogram rows are the slot's even when every output is written in place) */
 	}
 	kind = kind_of(c, unknown ? 0 : maxl, dev_bytes, ntot);   /* one shape for the whole group */
@@ -1406,6 +1587,8 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 		HIPCHK(hipEventRecord(s->kev1, s->stream));
 	s->timed = c->timing;
 	if (h_sidx && (rc = group_steer(c, s, b, nb, rsz, out_direct, h_sidx, h_sqs, &go)))
+		return rc;
+	if (fwd && (rc = group_fwd(c, s, b, nb, rsz, out_direct, &fo)))
 		return rc;
 	/* results: one copy when the host buffers follow each other, else per batch */
 	for (i = 0, pre = 0; !out_direct && i < nb;) {
@@ -1836,8 +2019,10 @@ static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
  * part rounded to 256 bytes): tx_frames as `nrings` rings (MOSRX_OP_FWD: one),
  * each with room for every frame of the batch sent whole (its frame bytes + 32
  * a frame; the rings together at most 4 GiB), tx_off, tx_src, tx_len, tx_nif,
- * tx_count / the ring rows, scratch. */
-#define OP_IS_FWD(op) ((op) == MOSRX_OP_FWD_PLAN || (op) == MOSRX_OP_FWD || (op) == MOSRX_OP_FWD_RINGS)
+ * tx_count / the ring rows, scratch.  MOSRX_OP_FWD_DESC takes the same block:
+ * its tx_mac (12 bytes an entry) lies where the rings would (each has room for
+ * 32 bytes a frame). */
+#define OP_IS_FWD(op) ((op) == MOSRX_OP_FWD_PLAN || (op) == MOSRX_OP_FWD || (op) == MOSRX_OP_FWD_RINGS || (op) == MOSRX_OP_FWD_DESC)
 static int fwd_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, uint32_t nrings)
 {
 	uint32_t i, maxn = 0;
@@ -1924,7 +2109,8 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 	}
 	case MOSRX_OP_FWD_PLAN:
 	case MOSRX_OP_FWD:
-	case MOSRX_OP_FWD_RINGS: {
+	case MOSRX_OP_FWD_RINGS:
+	case MOSRX_OP_FWD_DESC: {
 		uint32_t k = 0;
 		uint8_t *blk, *toff, *tsrc, *tlen, *tnif, *tcnt, *scr;
 		const size_t w = STEER_TMP_RND((size_t)c->fwd_tmp_n * 4);
@@ -1940,6 +2126,10 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 		tnif = tlen + STEER_TMP_RND((size_t)c->fwd_tmp_n * 2);
 		tcnt = tnif + STEER_TMP_RND(c->fwd_tmp_n);
 		scr = tcnt + 256;
+		if (op == MOSRX_OP_FWD_DESC)
+			return mosrx_fwd_desc_rings_dev(c, b, (const mosrx_fwd *)aux, c->fwd_tmp_rings, (uint32_t *)tsrc, (uint16_t *)tlen,
+			                                (uint32_t *)blk, (mosrx_fwd_ring *)tcnt, scr,
+			                                STEER_TMP_RND(mosrx_fwd_desc_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)), s);
 		if (op == MOSRX_OP_FWD_RINGS)
 			return mosrx_fwd_build_rings_dev(c, b, (const mosrx_fwd *)aux, blk, c->fwd_tmp_cap, c->fwd_tmp_rings,
 			                                 (uint32_t *)toff, (uint16_t *)tlen, (uint32_t *)tsrc, (mosrx_fwd_ring *)tcnt,
@@ -2035,7 +2225,7 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 {
 	int rc;
 	if (!c || !b || nb == 0 || iters == 0 || nstreams == 0 || nstreams > MOSRX_MAX_STREAMS ||
-	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_RINGS || (op != MOSRX_OP_TX_CSUM && !out) ||
+	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_DESC || (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
 	      OP_IS_FWD(op)) && !aux) ||
 	    (OP_IS_FWD(op) && (((arg & 0xFF) != 8 && (arg & 0xFF) != 16) || (arg >> 8) < 0 ||
@@ -2048,7 +2238,7 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 		return rc;
 	if (op == MOSRX_OP_FWD && (rc = fwd_tmp_reserve(c, b, nb, 1)))
 		return rc;
-	if (op == MOSRX_OP_FWD_RINGS) {
+	if (op == MOSRX_OP_FWD_RINGS || op == MOSRX_OP_FWD_DESC) {
 		if (!c->d_fwd)
 			return -ENOENT;
 		if ((rc = fwd_tmp_reserve(c, b, nb, c->fwd_num_netdevs ? c->fwd_num_netdevs : 1)))
@@ -2116,7 +2306,7 @@ int mosrx_time_op_dispatch(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, 
                            void *const *aux, uint32_t iters, float *avg_ms)
 {
 	struct op_run r = {op, arg, b, nb, out, aux};
-	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_RINGS ||
+	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_DESC ||
 	    (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
 	      OP_IS_FWD(op)) && !aux))
@@ -2267,6 +2457,10 @@ struct mosrx_queue {
 	size_t fscratch_rows;
 	uint32_t fwd_tiles, fwd_nrings, fwd_cap_units;
 	int fwd, fwd_build;
+	/* its descriptor form (mosrx_queue_set_fwd_desc): the store launch's table,
+	 * parallel to d_fdesc; fwd_desc: attached (then fwd is set, fwd_build is not) */
+	mosrx_ddesc *d_ddesc;
+	int fwd_desc;
 };
 
 int mosrx_queue_create_ex(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, void *const *d_out,
@@ -2696,6 +2890,8 @@ void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 		hipFree(q->d_fdesc);
 	if (q->d_fscratch)
 		hipFree(q->d_fscratch);
+	if (q->d_ddesc)
+		hipFree(q->d_ddesc);
 	free(q->h_desc);
 	free(q->d_match);
 	free(q);
@@ -2827,7 +3023,7 @@ int mosrx_fwd_set(mosrx_ctx *c, const mosrx_fwd_tables *t)
 	return 0;
 }
 
-/* A launch that reads the installed tables is about to go to stream s. */
+/* A launch that reads the installed tables is about to go to stream. */
 static void fwd_mark_used(mosrx_ctx *c)
 {
 	c->fwd_pool_used[(c->fwd_pool_next + MOSRX_FWD_POOL - 1) % MOSRX_FWD_POOL] = 1;
@@ -2967,7 +3163,7 @@ static int queue_fwd_check(const mosrx_ctx *c, const mosrx_queue *q)
 {
 	if (!c->d_fwd)
 		return -ENOENT;
-	if (q->fwd_build && q->fwd_nrings < c->fwd_num_netdevs)
+	if ((q->fwd_build || q->fwd_desc) && q->fwd_nrings < c->fwd_num_netdevs)
 		return -EINVAL;
 	return 0;
 }
@@ -2993,7 +3189,18 @@ static int queue_fwd(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 	fq.cap_units = q->fwd_cap_units;
 	HIPCHK(hipSetDevice(c->device));
 	fwd_mark_used(c);
-	rc = mosrx_launch_fwd_queue(&fq, q->fwd_build, (void *)s);
+	if (q->fwd_desc) {
+		mosrx_dqparams dq;
+		memset(&dq, 0, sizeof(dq));
+		dq.desc = q->d_ddesc;
+		dq.tab = fq.tab;
+		dq.scratch = fq.scratch;
+		dq.nb = fq.nb;
+		dq.total_tiles = fq.total_tiles;
+		dq.nrings = fq.nrings;
+		rc = mosrx_launch_fwd_desc_queue(&fq, &dq, (void *)s);
+	} else
+		rc = mosrx_launch_fwd_queue(&fq, q->fwd_build, (void *)s);
 	mosrx__note_stream(c, s);   /* (after the launches: its event covers them) */
 	return rc;
 }
@@ -3007,9 +3214,12 @@ int mosrx_queue_set_fwd(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd *f)
 	if (!c || !q)
 		return -EINVAL;
 	if (!f) {
-		q->fwd = q->fwd_build = 0;
+		if (!q->fwd_desc)   /* (the descriptor form is detached by its own call) */
+			q->fwd = q->fwd_build = 0;
 		return 0;
 	}
+	if (q->fwd_desc)
+		return -EINVAL;
 	build = f->d_tx_frames || f->d_tx_off || f->d_tx_len || f->d_tx_src || f->d_rings;
 	if (!f->d_plan || (build && (!f->d_tx_frames || !f->d_tx_off || !f->d_tx_len || !f->d_tx_src || !f->d_rings)))
 		return -EINVAL;
@@ -3085,6 +3295,153 @@ int mosrx_queue_set_fwd(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd *f)
 	q->fwd_nrings = build ? f->nrings : 0;
 	q->fwd_cap_units = build ? (uint32_t)(f->ring_cap / 16) : 0;
 	q->fwd_build = build;
+	q->fwd = 1;
+	return 0;
+}
+
+/* ---- the descriptor form of the ring build ---- */
+
+size_t mosrx_fwd_desc_scratch_bytes(uint32_t n, uint32_t nrings)
+{
+	return mosrx_fwd_rings_scratch_bytes(n, nrings);
+}
+
+int mosrx_fwd_desc_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint32_t nrings,
+                             uint32_t *d_tx_src, uint16_t *d_tx_len, uint32_t *d_tx_mac, mosrx_fwd_ring *d_rings,
+                             void *d_scratch, size_t scratch_bytes, void *stream)
+{
+	mosrx_fparams fp;
+	mosrx_dparams dp;
+	hipStream_t s;
+	int rc;
+	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || !d_tx_src || ((uintptr_t)d_tx_src & 3) || !d_tx_len ||
+	    ((uintptr_t)d_tx_len & 1) || !d_tx_mac || ((uintptr_t)d_tx_mac & 3) || !d_rings || ((uintptr_t)d_rings & 15) ||
+	    !d_scratch || ((uintptr_t)d_scratch & 15) || nrings < 1 || nrings > MOSRX_FWD_MAX_NETDEVS ||
+	    scratch_bytes < mosrx_fwd_desc_scratch_bytes(b->n, nrings))
+		return -EINVAL;
+	if ((rc = fwd_batch(c, b, &fp)))
+		return rc;
+	if (!c->d_fwd)
+		return -ENOENT;
+	if (nrings < c->fwd_num_netdevs)
+		return -EINVAL;
+	memset(&dp, 0, sizeof(dp));
+	dp.frames = fp.frames;
+	dp.off = fp.off;
+	dp.tab = fp.tab;
+	dp.plan = d_plan;
+	dp.frames_bytes = fp.frames_bytes;
+	dp.n = fp.n;
+	dp.nrings = nrings;
+	dp.tiles = (b->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+	dp.tx_src = d_tx_src;
+	dp.tx_len = d_tx_len;
+	dp.tx_mac = d_tx_mac;
+	dp.rings = d_rings;
+	dp.scratch = (uint32_t *)d_scratch;
+	s = stream ? (hipStream_t)stream : c->stream;
+	HIPCHK(hipSetDevice(c->device));
+	fwd_mark_used(c);
+	rc = mosrx_launch_fwd_desc(&dp, (void *)s);
+	mosrx__note_stream(c, s);
+	return rc;
+}
+
+int mosrx_queue_set_fwd_desc(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd_desc *f)
+{
+	mosrx_fdesc *h;
+	mosrx_ddesc *g;
+	uint32_t i, tiles = 0;
+	size_t rows;
+	if (!c || !q)
+		return -EINVAL;
+	if (!f) {
+		if (q->fwd_desc)
+			q->fwd = q->fwd_desc = 0;
+		return 0;
+	}
+	if (q->fwd && !q->fwd_desc)   /* mosrx_queue_set_fwd's attachment is in place */
+		return -EINVAL;
+	if (!f->d_plan || !f->d_tx_src || !f->d_tx_len || !f->d_tx_mac || !f->d_rings || f->nrings < 1 ||
+	    f->nrings > MOSRX_FWD_MAX_NETDEVS)
+		return -EINVAL;
+	for (i = 0; i < q->nb; i++) {
+		if (f->in_ifidx && f->in_ifidx[i] >= MOSRX_FWD_MAX_NETDEVS)
+			return -EINVAL;
+		if (!f->d_rings[i] || ((uintptr_t)f->d_rings[i] & 15))
+			return -EINVAL;
+		if (!q->h_desc[i].n)
+			continue;
+		if (!f->d_plan[i] || ((uintptr_t)f->d_plan[i] & 7) || ((uintptr_t)q->h_desc[i].off & 3) ||
+		    ((uintptr_t)q->h_desc[i].len & 1) || !f->d_tx_src[i] || ((uintptr_t)f->d_tx_src[i] & 3) || !f->d_tx_len[i] ||
+		    ((uintptr_t)f->d_tx_len[i] & 1) || !f->d_tx_mac[i] || ((uintptr_t)f->d_tx_mac[i] & 3))
+			return -EINVAL;
+	}
+	h = calloc(q->nb, sizeof(*h));
+	g = calloc(q->nb, sizeof(*g));
+	if (!h || !g) {
+		free(h);
+		free(g);
+		return -ENOMEM;
+	}
+	for (i = 0; i < q->nb; i++) {
+		const mosrx_qdesc *d = &q->h_desc[i];
+		h[i].n = g[i].n = d->n;
+		h[i].tile_base = g[i].tile_base = tiles;
+		h[i].in_ifidx = f->in_ifidx ? f->in_ifidx[i] : 0;
+		h[i].rings = g[i].rings = f->d_rings[i];
+		tiles += (d->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+		if (!d->n)
+			continue;
+		h[i].frames = g[i].frames = d->frames;
+		h[i].off = g[i].off = d->off;
+		h[i].len = d->len;
+		h[i].rec = (const uint8_t *)d->out;
+		h[i].frames_bytes = g[i].frames_bytes = d->frames_bytes;
+		h[i].plan = f->d_plan[i];
+		g[i].plan = f->d_plan[i];
+		g[i].tx_src = f->d_tx_src[i];
+		g[i].tx_len = f->d_tx_len[i];
+		g[i].tx_mac = f->d_tx_mac[i];
+	}
+	/* from here a failure leaves the queue without forwarding, as mosrx_queue_set_fwd's does */
+	q->fwd = q->fwd_build = q->fwd_desc = 0;
+	rows = ((size_t)tiles ? tiles : 1) * f->nrings;
+	if (hipSetDevice(c->device) != hipSuccess) {
+		free(h);
+		free(g);
+		return -EIO;
+	}
+	if (rows > q->fscratch_rows) {
+		if (q->d_fscratch)
+			hipFree(q->d_fscratch);
+		q->d_fscratch = NULL;
+		q->fscratch_rows = 0;
+		if (hipMalloc((void **)&q->d_fscratch, rows * MOSRX_FWD_ROW) != hipSuccess) {
+			free(h);
+			free(g);
+			return -ENOMEM;
+		}
+		q->fscratch_rows = rows;
+	}
+	if ((!q->d_fdesc && hipMalloc((void **)&q->d_fdesc, (size_t)q->nb * sizeof(*h)) != hipSuccess) ||
+	    (!q->d_ddesc && hipMalloc((void **)&q->d_ddesc, (size_t)q->nb * sizeof(*g)) != hipSuccess)) {
+		free(h);
+		free(g);
+		return -ENOMEM;
+	}
+	if (hipMemcpy(q->d_fdesc, h, (size_t)q->nb * sizeof(*h), hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(q->d_ddesc, g, (size_t)q->nb * sizeof(*g), hipMemcpyHostToDevice) != hipSuccess) {
+		free(h);
+		free(g);
+		return -EIO;
+	}
+	free(h);
+	free(g);
+	q->fwd_tiles = tiles;
+	q->fwd_nrings = f->nrings;
+	q->fwd_cap_units = 0;
+	q->fwd_desc = 1;
 	q->fwd = 1;
 	return 0;
 }

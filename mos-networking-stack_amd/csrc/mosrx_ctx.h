@@ -91,6 +91,20 @@ struct slot {
 	mosrx_xdesc *h_xdesc, *d_xdesc;
 	uint32_t *d_sqfh, *d_sqmt;
 	mosrx_tcpinfo *d_sqti;
+	/* forwarding of a group (mosrx_slot_fwd): the armed outputs (fwd_armed; taken
+	 * by the next group submit), the two batch tables of the descriptor queue
+	 * form (pinned, copied to the device per armed submit), the ring rows of
+	 * every batch, and the buffers slot_reserve sizes with the rest: plan and
+	 * entries for cap_n frames, a scratch row per ring and tile a group of cap_n
+	 * frames in MOSRX_MAX_GROUP batches can have */
+	mosrx_slot_fwd_out fwd;
+	int fwd_armed;
+	mosrx_fdesc *h_fdesc, *d_fdesc;
+	mosrx_ddesc *h_ddesc, *d_ddesc;
+	mosrx_fwd_ring *d_frings;
+	mosrx_fwd *d_fplan;
+	uint32_t *d_ftsrc, *d_ftmac, *d_fscr;
+	uint16_t *d_ftlen;
 	int timed;
 	int busy;
 };

@@ -139,6 +139,64 @@ _Static_assert(sizeof(mosrx_fdesc) == 96 && sizeof(mosrx_fqparams) == 56, "queue
  * queue of empty batches launches the scan alone (every rings[q] = {0,0,0,0}). */
 int mosrx_launch_fwd_queue(const mosrx_fqparams *fq, int with_build, void *stream);
 
+/* The descriptor form of the ring build (mosrx_fwd_desc_rings_dev): per sent
+ * frame its source index, TX length and 12 rewritten address bytes in place of
+ * the frame.  Scratch as the ring form's. */
+typedef struct mosrx_dparams {
+	const uint8_t  *frames;
+	const uint32_t *off;
+	const mosrx_fwd_dev *tab;
+	const mosrx_fwd *plan;       /* n, 8-byte aligned */
+	uint32_t frames_bytes, n;
+	uint32_t nrings;             /* 1 .. MOSRX_FWD_MAX_NETDEVS */
+	uint32_t tiles;
+	uint32_t *tx_src;
+	uint16_t *tx_len;
+	uint32_t *tx_mac;            /* three dwords per entry */
+	mosrx_fwd_ring *rings;       /* nrings, 16-byte aligned */
+	uint32_t *scratch;           /* max(tiles, 1) * nrings rows */
+} mosrx_dparams;
+
+/* Its three launches (the ring form's totals and scan, then the store) on
+ * `stream`; 0, -EINVAL or -EIO.  n == 0: the scan alone. */
+int mosrx_launch_fwd_desc(const mosrx_dparams *dp, void *stream);
+
+/* Its batch-queue form (mosrx_queue_set_fwd_desc): the plan, totals and scan
+ * launches read the queue's mosrx_fdesc table (tx and tx_off unused), the store
+ * launch this one, built over the same tile_base[]. */
+typedef struct mosrx_ddesc {
+	const uint8_t  *frames;
+	const uint32_t *off;
+	const mosrx_fwd *plan;
+	uint32_t       *tx_src;
+	uint16_t       *tx_len;
+	uint32_t       *tx_mac;
+	mosrx_fwd_ring *rings;
+	uint32_t frames_bytes, n;
+	uint32_t tile_base;
+	uint32_t pad;
+} mosrx_ddesc;
+
+typedef struct mosrx_dqparams {
+	const mosrx_ddesc   *desc;   /* nb, device-resident */
+	const mosrx_fwd_dev *tab;
+	uint32_t *scratch;           /* the fqparams' */
+	uint32_t nb, total_tiles;
+	uint32_t nrings;
+	uint32_t pad;
+} mosrx_dqparams;
+
+#ifdef __cplusplus
+static_assert(sizeof(mosrx_ddesc) == 72 && sizeof(mosrx_dqparams) == 40, "descriptor queue form: 72-byte descriptor, 40-byte parameters");
+#else
+_Static_assert(sizeof(mosrx_ddesc) == 72 && sizeof(mosrx_dqparams) == 40, "descriptor queue form: 72-byte descriptor, 40-byte parameters");
+#endif
+
+/* Plan, totals, scan (one workgroup per batch) and store over every batch of
+ * the queue: four launches whatever nb is; 0, -EINVAL or -EIO.  fq->cap_units
+ * is not looked at.  A queue of empty batches launches the scan alone. */
+int mosrx_launch_fwd_desc_queue(const mosrx_fqparams *fq, const mosrx_dqparams *dq, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

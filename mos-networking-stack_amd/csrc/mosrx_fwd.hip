@@ -616,6 +616,122 @@ __global__ __launch_bounds__(MOSRX_FWD_THREADS) void mosrx_fwd_ring_copy_queue_k
 #include "mosrx_fwd_rings_body.inc"
 }
 
+// ---- build, descriptor ring form --------------------------------------------
+// What a host that still holds the received frames lacks per sent frame: its
+// netdev and place in it (the entry index), its source index, its TX length and
+// the 12 address bytes EthernetOutput rewrites.  The ring form's totals and scan
+// launches as they are (neither reads a capacity), then
+//   3. store   per tile: the frame's rank among the tile's frames of its own
+//              netdev (the same masked scan), its entry = the scan's entry base
+//              + rank; tx_src / tx_len / the three tx_mac dwords stored by the
+//              frame's own lane.  count and units are sums over the tiles, by
+//              atomics on what the scan zeroed: neither depends on the order
+//              the workgroups run in.
+// Nothing is dropped, so units is the ring's whole need: what a byte ring
+// large enough reports.
+__device__ __forceinline__ void fwd_desc_store_body(const mosrx_dparams &p, uint32_t blk)
+{
+	__shared__ uint32_t s_wu[FWD_WAVES][FWD_NQ], s_wc[FWD_WAVES][FWD_NQ];
+	// uniform over the workgroup (blk and p.tiles are the same in every lane): all
+	// of its lanes leave here or all reach the barrier in fwd_ring_tile_scan
+	if (blk >= p.tiles)
+		return;
+	const uint32_t nrings = min(p.nrings, FWD_NQ);
+	const uint32_t t = threadIdx.x, i = blk * MOSRX_FWD_TILE + t;
+	u32x2 pl = {0u, 0u};
+	uint32_t o = 0;
+	if (i < p.n) {
+		pl = *reinterpret_cast<const u32x2 *>(p.plan + i);
+		o = p.off[i];
+	}
+	uint32_t q, excl, rank;
+	const uint32_t units = fwd_ring_units(pl, nrings, q);
+	const bool sent = units != 0u;   // (then q < nrings and i < n)
+	fwd_ring_tile_scan(q, units, nrings, s_wu, s_wc, excl, rank);
+	uint32_t base = 0;
+	if (sent)
+		base = p.scratch[4u * ((uint64_t)blk * nrings + q) + 2u];
+	const uint32_t j = base + rank;
+	if (sent && j < p.n) {
+		// bytes 0 .. 11 of the frame the byte-ring copy writes (its r == 0 unit)
+		const __amdgpu_buffer_rsrc_t rs = frame_rsrc(p.frames, p.frames_bytes);
+		const mosrx_fwd_dev *T = p.tab;
+		const u32x4 h = fwd_ld128(rs, o);
+		u32x3 m = {h.x, h.y, h.z};
+		if ((pl.x >> 24) == MOSRX_FWD_IP) {
+			const uint32_t ai = pl.y & 0xFFFFu;
+			const uint32_t nif = q & (MOSRX_FWD_MAX_NETDEVS - 1u);
+			const uint32_t *sm = reinterpret_cast<const uint32_t *>(T->netdev_haddr[nif]);
+			const uint32_t s0 = sm[0], s1 = sm[1] & 0xFFFFu;
+			uint32_t d0 = h.x, d1 = h.y & 0xFFFFu;   // the frame's own h_dest (nic_forward_table path)
+			if (ai < MOSRX_FWD_MAX_ARP) {
+				const uint32_t *dm = reinterpret_cast<const uint32_t *>(T->a_haddr[ai]);
+				d0 = dm[0];
+				d1 = dm[1] & 0xFFFFu;
+			}
+			m.x = d0;
+			m.y = d1 | (s0 << 16);
+			m.z = (s0 >> 16) | (s1 << 16);
+		}
+		p.tx_src[j] = i;
+		p.tx_len[j] = (uint16_t)(pl.x & 0xFFFFu);
+		uint32_t *mac = p.tx_mac + 3u * (uint64_t)j;
+		mac[0] = m.x;
+		mac[1] = m.y;
+		mac[2] = m.z;
+	}
+	if (t < nrings) {
+		uint32_t tu = 0, tc = 0;
+#pragma unroll
+		for (uint32_t w = 0; w < FWD_WAVES; w++) {
+			tu += s_wu[w][t];
+			tc += s_wc[w][t];
+		}
+		mosrx_fwd_ring *rg = p.rings + t;
+		if (tc) {
+			atomicAdd(&rg->count, tc);
+			atomicAdd(&rg->units, tu);
+		}
+	}
+}
+
+__global__ __launch_bounds__(MOSRX_FWD_THREADS) void mosrx_fwd_desc_store_kernel(mosrx_dparams p)
+{
+	fwd_desc_store_body(p, blockIdx.x);
+}
+
+// The store launch over every batch of a queue: its own descriptor table, the
+// same tile_base[] as the plan / totals launches', found the same way.
+__global__ __launch_bounds__(MOSRX_FWD_THREADS) void mosrx_fwd_desc_store_queue_kernel(mosrx_dqparams dq)
+{
+	if (blockIdx.x >= dq.total_tiles)
+		return;
+	uint32_t lo = 0, hi = dq.nb;
+	for (int it = 0; it < 32 && hi - lo > 1; it++) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (dq.desc[mid].tile_base <= blockIdx.x)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	const mosrx_ddesc d = dq.desc[lo];
+	mosrx_dparams p = {};
+	p.frames = d.frames;
+	p.off = d.off;
+	p.tab = dq.tab;
+	p.plan = d.plan;
+	p.frames_bytes = d.frames_bytes;
+	p.n = d.n;
+	p.nrings = dq.nrings;
+	p.tiles = (d.n + MOSRX_FWD_TILE - 1u) / MOSRX_FWD_TILE;
+	p.tx_src = d.tx_src;
+	p.tx_len = d.tx_len;
+	p.tx_mac = d.tx_mac;
+	p.rings = d.rings;
+	p.scratch = dq.scratch + 4u * ((uint64_t)d.tile_base * min(dq.nrings, FWD_NQ));
+	fwd_desc_store_body(p, blockIdx.x - d.tile_base);
+}
+
 static int fwd_common_ok(const mosrx_fparams *fp)
 {
 	return fp && fp->tab && fp->plan && !((uintptr_t)fp->plan & 7) &&
@@ -697,5 +813,58 @@ extern "C" int mosrx_launch_fwd_queue(const mosrx_fqparams *fq, int with_build, 
 		if (fq->total_tiles)
 			hipLaunchKernelGGL(mosrx_fwd_ring_copy_queue_kernel, grid, block, 0, s, *fq);
 	}
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+static int fwd_desc_ok(const mosrx_dparams *dp)
+{
+	return dp && dp->tab && dp->plan && !((uintptr_t)dp->plan & 7) &&
+	       (dp->n == 0 || (dp->frames && dp->off && !((uintptr_t)dp->off & 3))) && dp->tx_src &&
+	       !((uintptr_t)dp->tx_src & 3) && dp->tx_len && !((uintptr_t)dp->tx_len & 1) && dp->tx_mac &&
+	       !((uintptr_t)dp->tx_mac & 3) && dp->rings && !((uintptr_t)dp->rings & 15) && dp->scratch &&
+	       !((uintptr_t)dp->scratch & 15) && dp->nrings >= 1u && dp->nrings <= FWD_NQ &&
+	       dp->tiles == (dp->n + MOSRX_FWD_TILE - 1u) / MOSRX_FWD_TILE;
+}
+
+extern "C" int mosrx_launch_fwd_desc(const mosrx_dparams *dp, void *stream)
+{
+	const hipStream_t s = (hipStream_t)stream;
+	if (!fwd_desc_ok(dp))
+		return -EINVAL;
+	// the ring form's totals and scan read the plan, the scratch rows and the rings only
+	mosrx_rparams rp = {};
+	rp.plan = dp->plan;
+	rp.n = dp->n;
+	rp.nrings = dp->nrings;
+	rp.tiles = dp->tiles;
+	rp.rings = dp->rings;
+	rp.scratch = dp->scratch;
+	if (dp->tiles)
+		hipLaunchKernelGGL(mosrx_fwd_ring_totals_kernel, dim3(dp->tiles), dim3(MOSRX_FWD_THREADS), 0, s, rp);
+	hipLaunchKernelGGL(mosrx_fwd_ring_scan_kernel, dim3(1), dim3(FWD_SCAN_THREADS), 0, s, rp);
+	if (dp->tiles)
+		hipLaunchKernelGGL(mosrx_fwd_desc_store_kernel, dim3(dp->tiles), dim3(MOSRX_FWD_THREADS), 0, s, *dp);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+extern "C" int mosrx_launch_fwd_desc_queue(const mosrx_fqparams *fq, const mosrx_dqparams *dq, void *stream)
+{
+	const hipStream_t s = (hipStream_t)stream;
+	if (!fq || !fq->desc || !fq->tab || fq->nb == 0 || (fq->rec_bytes != 8u && fq->rec_bytes != 16u) || !fq->scratch ||
+	    ((uintptr_t)fq->scratch & 15) || fq->nrings < 1u || fq->nrings > FWD_NQ || !dq || !dq->desc ||
+	    dq->tab != fq->tab || dq->scratch != fq->scratch || dq->nb != fq->nb || dq->total_tiles != fq->total_tiles ||
+	    dq->nrings != fq->nrings)
+		return -EINVAL;
+	const dim3 grid(fq->total_tiles), block(MOSRX_FWD_THREADS);
+	if (fq->total_tiles) {
+		if (fq->rec_bytes == 8u)
+			hipLaunchKernelGGL(mosrx_fwd_plan_queue_kernel<8u>, grid, block, 0, s, *fq);
+		else
+			hipLaunchKernelGGL(mosrx_fwd_plan_queue_kernel<16u>, grid, block, 0, s, *fq);
+		hipLaunchKernelGGL(mosrx_fwd_ring_totals_queue_kernel, grid, block, 0, s, *fq);
+	}
+	hipLaunchKernelGGL(mosrx_fwd_ring_scan_queue_kernel, dim3(fq->nb), dim3(FWD_SCAN_THREADS), 0, s, *fq);
+	if (fq->total_tiles)
+		hipLaunchKernelGGL(mosrx_fwd_desc_store_queue_kernel, grid, block, 0, s, *dq);
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }

@@ -119,6 +119,7 @@ BPF_MAX_PROGS = 32
 OP_FWD_PLAN = 10       # MOSRX_OP_FWD_PLAN: the forwarding plan (arg = rec_bytes | in_ifidx << 8)
 OP_FWD = 11            # MOSRX_OP_FWD: plan + build
 OP_FWD_RINGS = 12      # MOSRX_OP_FWD_RINGS: plan + the ring form of the build (one ring per netdev)
+OP_FWD_DESC = 13       # MOSRX_OP_FWD_DESC: plan + the descriptor form of the ring build
 FWD_MAX_ROUTES, FWD_MAX_ARP, FWD_MAX_NETDEVS = 128, 1024, 16
 FWD_NONE, FWD_IP, FWD_ETH, FWD_NO_ROUTE, FWD_NO_ARP, FWD_NO_NIC = range(6)   # MOSRX_FWD_*
 # mosrx_fwd: the plan of one frame
@@ -152,6 +153,18 @@ class QueueFwd(C.Structure):
     _fields_ = [("in_ifidx", C.c_void_p), ("d_plan", C.c_void_p), ("ring_cap", C.c_uint64), ("nrings", C.c_uint32),
                 ("d_tx_frames", C.c_void_p), ("d_tx_off", C.c_void_p), ("d_tx_len", C.c_void_p),
                 ("d_tx_src", C.c_void_p), ("d_rings", C.c_void_p)]
+
+
+class QueueFwdDesc(C.Structure):
+    """mosrx_queue_fwd_desc: the descriptor form attached to a batch queue (Queue.set_fwd_desc)."""
+    _fields_ = [("in_ifidx", C.c_void_p), ("d_plan", C.c_void_p), ("nrings", C.c_uint32), ("d_tx_src", C.c_void_p),
+                ("d_tx_len", C.c_void_p), ("d_tx_mac", C.c_void_p), ("d_rings", C.c_void_p)]
+
+
+class SlotFwdOut(C.Structure):
+    """mosrx_slot_fwd_out: forwarding outputs armed on a slot's next group submit (Context.slot_fwd)."""
+    _fields_ = [("in_ifidx", C.c_void_p), ("nrings", C.c_uint32), ("h_plan", C.c_void_p), ("h_tx_src", C.c_void_p),
+                ("h_tx_len", C.c_void_p), ("h_tx_mac", C.c_void_p), ("h_rings", C.c_void_p)]
 
 
 def conf_mask(prefix: int) -> int:
@@ -483,6 +496,12 @@ def lib():
             "mosrx_fwd_rings_scratch_bytes": (C.c_size_t, [U32, U32]),
             "mosrx_fwd_tile": (U32, []),
             "mosrx_queue_set_fwd": (I, [P, P, C.POINTER(QueueFwd)]),
+            "mosrx_fwd_desc_rings_dev": (I, [P, C.POINTER(Batch), P, U32, P, P, P, P, P, C.c_size_t, P]),
+            "mosrx_fwd_desc_scratch_bytes": (C.c_size_t, [U32, U32]),
+            "mosrx_queue_set_fwd_desc": (I, [P, P, C.POINTER(QueueFwdDesc)]),
+            "mosrx_slot_fwd": (I, [P, I, C.POINTER(SlotFwdOut)]),
+            "mosrx_gpu_module_set_fwd": (I, [C.POINTER(FwdTables), I]),
+            "mosrx_backend_forward": (I, [P, P, I, P]),
             "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
             "mosrx_hub_endpoint": (P, [P, U32]),
             "mosrx_hub_stats_get": (I, [P, P]),
@@ -1018,6 +1037,32 @@ class Context:
         if sync:
             _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
 
+    def fwd_desc_rings_dev(self, b: Batch, d_plan: int, nrings: int, d_tx_src: int, d_tx_len: int, d_tx_mac: int,
+                           d_rings: int, d_scratch: int, scratch_bytes: int, sync: bool = True,
+                           stream: int | None = None) -> None:
+        """mosrx_fwd_desc_rings_dev: per sent frame of a planned batch its source index,
+        TX length and 12 rewritten address bytes, sorted by output netdev (d_rings:
+        nrings records of FWD_RING_DTYPE); the frames themselves stay where they are."""
+        _chk(lib().mosrx_fwd_desc_rings_dev(self.handle, C.byref(b), d_plan, nrings, d_tx_src, d_tx_len, d_tx_mac,
+                                            d_rings, d_scratch, scratch_bytes, stream), "mosrx_fwd_desc_rings_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
+    def slot_fwd(self, slot: int, tx_src: list | None, tx_len: list | None = None, tx_mac: list | None = None,
+                 rings: list | None = None, nrings: int = 0, in_ifidx: list | None = None,
+                 plan: list | None = None) -> None:
+        """mosrx_slot_fwd: arm the slot's next group submit with the plan and the
+        descriptor form of the ring build (host pointers per batch); tx_src None disarms."""
+        if tx_src is None:
+            self._fwd_arm = None
+            _chk(lib().mosrx_slot_fwd(self.handle, slot, None), "mosrx_slot_fwd")
+            return
+        keep = [(C.c_void_p * len(a))(*a) if a is not None else None for a in (plan, tx_src, tx_len, tx_mac, rings)]
+        ifs = (C.c_uint8 * len(in_ifidx))(*in_ifidx) if in_ifidx is not None else None
+        o = SlotFwdOut(C.cast(ifs, C.c_void_p), nrings, *[C.cast(a, C.c_void_p) for a in keep])
+        self._fwd_arm = (keep, ifs, o)   # the pointer arrays must outlive the submit
+        _chk(lib().mosrx_slot_fwd(self.handle, slot, C.byref(o)), "mosrx_slot_fwd")
+
     def slot_steer(self, slot: int, idx: list | None, qstart: list | None) -> None:
         """mosrx_slot_steer: arm the slot's next group submit (host pointers per
         batch: n indices, STEER_QSLOTS queue starts); None, None disarms."""
@@ -1139,18 +1184,18 @@ class Context:
                 d.d_match = DevBuffer(self, max(d.n * 4, 4))
             if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) and d.d_sidx is None:
                 d.d_sidx = DevBuffer(self, max(d.n * 4, 4))
-            if op in (OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS) and d.d_fplan is None:
+            if op in (OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS, OP_FWD_DESC) and d.d_fplan is None:
                 d.d_fplan = DevBuffer(self, max(d.n * 8, 8))
         bs = (Batch * len(dbs))(*[d.batch() for d in dbs])
         # OP_STEER reads the records a classify call left: the compact ones for arg == 8
         outs = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_BPF else
                                           d.d_out8.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE,
-                                                                 OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS) and (arg & 0xFF) == 8
+                                                                 OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS, OP_FWD_DESC) and (arg & 0xFF) == 8
                                           else d.d_out.ptr) for d in dbs])
         aux = (C.c_void_p * len(dbs))(*[(d.d_match.ptr if op == OP_CLASSIFY_BPF else
                                          d.d_tinfo.ptr if op == OP_CLASSIFY_TI else
                                          d.d_sidx.ptr if op in (OP_STEER, OP_STEER_GATHER, OP_STEER_GATHER_SIDE) else
-                                         d.d_fplan.ptr if op in (OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS) else
+                                         d.d_fplan.ptr if op in (OP_FWD_PLAN, OP_FWD, OP_FWD_RINGS, OP_FWD_DESC) else
                                          (d.d_fhash.ptr if d.d_fhash else None)) for d in dbs])
         tot, avg = C.c_float(), C.c_float()
         _chk(lib().mosrx_time_op(self.handle, op, arg, bs, len(dbs), outs, aux, iters, nstreams,
@@ -1299,6 +1344,21 @@ class Queue:
                      *[C.cast(a, C.c_void_p) for a in keep[1:]])
         _chk(lib().mosrx_queue_set_fwd(self.ctx.handle, self.handle, C.byref(f)), "mosrx_queue_set_fwd")
 
+    def set_fwd_desc(self, plan: list | None, in_ifidx: list | None = None, nrings: int = 0,
+                     tx_src: list | None = None, tx_len: list | None = None, tx_mac: list | None = None,
+                     rings: list | None = None) -> None:
+        """mosrx_queue_set_fwd_desc: attach the plan and the descriptor form of the ring
+        build to every run -- per-batch device pointers; plan None detaches.  Not
+        together with set_fwd."""
+        if plan is None:
+            _chk(lib().mosrx_queue_set_fwd_desc(self.ctx.handle, self.handle, None), "mosrx_queue_set_fwd_desc")
+            return
+        keep = [(C.c_void_p * len(a))(*a) if a is not None else None for a in (plan, tx_src, tx_len, tx_mac, rings)]
+        ifs = (C.c_uint8 * len(in_ifidx))(*in_ifidx) if in_ifidx is not None else None
+        f = QueueFwdDesc(C.cast(ifs, C.c_void_p), C.cast(keep[0], C.c_void_p), nrings,
+                         *[C.cast(a, C.c_void_p) for a in keep[1:]])
+        _chk(lib().mosrx_queue_set_fwd_desc(self.ctx.handle, self.handle, C.byref(f)), "mosrx_queue_set_fwd_desc")
+
     def run(self, sync: bool = True):
         _chk(lib().mosrx_queue_run(self.ctx.handle, self.handle, None), "mosrx_queue_run")
         if sync:
@@ -1366,6 +1426,19 @@ PKT_RX_RESULTS8 = 0x18
 PKT_RX_STEER = 0x19
 PKT_RX_QUEUE = 0x1A
 PKT_RX_QUEUE_SIDE = 0x1B
+PKT_RX_FWD = 0x1C
+
+
+class FwdView(C.Structure):
+    """mosrx_fwd_view: dev_ioctl(MOSRX_PKT_RX_FWD)'s answer for the exposed batch."""
+    _fields_ = [("n", C.c_uint32), ("nrings", C.c_uint32), ("frames", C.c_void_p), ("off", C.c_void_p),
+                ("plan", C.c_void_p), ("tx_src", C.c_void_p), ("tx_len", C.c_void_p), ("tx_mac", C.c_void_p),
+                ("rings", C.c_void_p)]
+
+
+class FwdSendStats(C.Structure):
+    """mosrx_fwd_send_stats."""
+    _fields_ = [("sent", C.c_uint64), ("no_buffer", C.c_uint64), ("send_calls", C.c_uint64)]
 QUEUE_PROBE = 0xFFFFFFFF
 
 
@@ -1394,7 +1467,7 @@ class GpuBackend:
                  timing: bool = False, flowhash: bool = False, tx_csum: bool = False, compact: bool = False,
                  group_bytes: int = 0, group_max_us: int = 0, direct_kb: int | None = None,
                  direct_frames: int | None = None, module_lib=None, steer: bool | int = False,
-                 steer_one: int = 0):
+                 steer_one: int = 0, fwd: FwdTables | None = None, fwd_listener: bool = False):
         self.L = L = module_lib or lib()
         cfg = ModuleCfg()
         L.mosrx_gpu_module_cfg_default(C.byref(cfg))
@@ -1428,6 +1501,11 @@ class GpuBackend:
         # steered groups of batches up to this many frames: one steer launch (0: never; always set,
         # so a backend does not inherit an earlier one's)
         _chk(L.mosrx_gpu_module_set_steer_one(int(steer_one)), "mosrx_gpu_module_set_steer_one")
+        # forwarding on the GPU with these tables (None: off; always set, for the same reason)
+        L.mosrx_gpu_module_set_fwd.restype = C.c_int
+        L.mosrx_gpu_module_set_fwd.argtypes = [C.POINTER(FwdTables), C.c_int]
+        _chk(L.mosrx_gpu_module_set_fwd(C.byref(fwd) if fwd is not None else None, int(bool(fwd_listener))),
+             "mosrx_gpu_module_set_fwd")
         self.nif = len(sources)
         self.sources = list(sources)
         self.m = IoModuleFunc.in_dll(L, "gpu_module_func")
@@ -1519,6 +1597,31 @@ class GpuBackend:
         if self._ioctl(self.ctx, ifidx, PKT_RX_QUEUE_SIDE, C.byref(v)):
             return None
         return _queue_side_arrays(v)
+
+    def fwd_view(self, ifidx: int):
+        """dev_ioctl(MOSRX_PKT_RX_FWD): the exposed batch's (plan[n], tx_src[m], tx_len[m],
+        tx_mac[12 m] bytes, rings[nrings]) with m the rings' total count, or None when the
+        ioctl answers -1 (forwarding off, no batch, the batch was touched)."""
+        v = FwdView()
+        if self._ioctl(self.ctx, ifidx, PKT_RX_FWD, C.byref(v)):
+            return None
+
+        def arr(p, nbytes, dtype):
+            if not nbytes:
+                return np.zeros(0, dtype)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), (nbytes,)).view(dtype).copy()
+        rings = arr(v.rings, 16 * v.nrings, FWD_RING_DTYPE)
+        m = int(rings["count"].sum())
+        return (arr(v.plan, 8 * v.n, FWD_DTYPE), arr(v.tx_src, 4 * m, np.uint32), arr(v.tx_len, 2 * m, np.uint16),
+                arr(v.tx_mac, 12 * m, np.uint8), rings)
+
+    def forward(self, ifidx: int) -> tuple[int, FwdSendStats]:
+        """mosrx_backend_forward for the batch exposed on ifidx: (its return -- frames
+        sent, or -1 when the view is not there --, the send's stats)."""
+        st = FwdSendStats()
+        fn = self.L.mosrx_backend_forward
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        return int(fn(C.addressof(self.m), self.ctx, ifidx, C.byref(st))), st
 
     def run_loop_queues(self, nq: int, fn=None, args: list | None = None, max_rounds: int = 0) -> RxStats:
         """mosrx_rx_loop_queues over this backend: fn (a _PKTFN callback) gets
