@@ -632,6 +632,28 @@ typedef struct mosrx_slot_fwd_out {
 } mosrx_slot_fwd_out;
 int mosrx_slot_fwd(mosrx_ctx *c, int slot, const mosrx_slot_fwd_out *o);
 
+/* ---- the one-launch forwarding form: small batches, direct groups ------------- */
+/* The plan and the descriptor rings in one kernel, one workgroup per batch, for
+ * batches whose forwarding is bound by launch latency rather than by the walk:
+ * the same outputs as the four launches, byte for byte.  Per context and off by
+ * default: with a limit of max_frames > 0 every place that issues the plan and
+ * the descriptor form together (a mosrx_queue_run with mosrx_queue_set_fwd_desc
+ * attached, a group submit armed by mosrx_slot_fwd, MOSRX_OP_FWD_DESC) issues
+ * the one launch when every batch of that launch has n <= max_frames, and the
+ * four launches otherwise (one larger batch sends the whole launch there);
+ * mosrx_fwd_desc_rings_dev takes its plan as given and issues one launch in
+ * place of its three, leaving its scratch untouched.  0: the existing
+ * launches, always.  MOSRX_FWD_ONE_MAX bounds one workgroup's walk (32 tiles
+ * of 256 frames); a limit above it is -EINVAL and changes nothing.  The limit
+ * worth setting: DESIGN.md §4.13.  Refusals are those of the entry points and
+ * come before any launch.  The byte-ring forms, mosrx_fwd_plan_dev and a
+ * plan-only queue attachment are not affected. */
+#define MOSRX_FWD_ONE_MAX 8192u
+int      mosrx_set_fwd_one(mosrx_ctx *c, uint32_t max_frames);
+uint32_t mosrx_get_fwd_one(const mosrx_ctx *c);
+/* Forwarding launches of this context that took the one-launch form so far (n == 0 launches included). */
+uint64_t mosrx_fwd_one_count(const mosrx_ctx *c);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned

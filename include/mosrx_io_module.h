@@ -337,6 +337,15 @@ int  mosrx_gpu_module_get_cfg(mosrx_gpu_module_cfg *cfg);
  * module, not a field of mosrx_gpu_module_cfg: the struct's layout stands. */
 int     mosrx_gpu_module_set_steer_one(int32_t max_frames);
 int32_t mosrx_gpu_module_get_steer_one(void);
+/* With forwarding on (mosrx_gpu_module_set_fwd): a group whose batches all have
+ * at most max_frames frames gets its plan and descriptor rings from one launch
+ * instead of four (mosrx_set_fwd_one on every context opened afterwards: the
+ * same outputs, so MOSRX_PKT_RX_FWD, mosrx_backend_forward and the hub answer
+ * what they did; what to set).  Before init_handle.  0 (the
+ * default): never.  Negative or above MOSRX_FWD_ONE_MAX: -EINVAL, and the
+ * setting stays.  A setting of the module, like the one above. */
+int     mosrx_gpu_module_set_fwd_one(int32_t max_frames);
+int32_t mosrx_gpu_module_get_fwd_one(void);
 /* Bind a thread context pointer to a cpu index before init_handle.  Unbound
  * contexts get their cpu from ctx->cpu inside an mOS build (the mTCP core,
  * mtcp.h:306, set by MTCPRunThread before init_handle, core.c:1302-1313) and
@@ -392,6 +401,9 @@ int  mosrx_gpu_module_stats_of(struct mtcp_thread_context *ctx, mosrx_gpu_module
 /* Steered groups of this thread's contexts that took the one-launch form
  * (mosrx_gpu_module_set_steer_one; mosrx_steer_one_count summed over the netdevs). */
 uint64_t mosrx_gpu_module_steer_one_count(struct mtcp_thread_context *ctx);
+/* Forwarded groups of this thread's contexts that took the one-launch form
+ * (mosrx_gpu_module_set_fwd_one; mosrx_fwd_one_count summed over the netdevs). */
+uint64_t mosrx_gpu_module_fwd_one_count(struct mtcp_thread_context *ctx);
 
 /* ---- RunMainLoop-shaped driver (core.c:897-909) ---- */
 typedef struct mosrx_rx_stats {

@@ -171,6 +171,7 @@ static struct { struct mtcp_thread_context *ctx; int cpu; struct gpu_priv *priv;
 static mosrx_source *g_src_cpu[MAX_THREADS][MOSRX_MAX_DEVICES];
 static int g_next_cpu;
 static int32_t g_steer_one;   /* mosrx_gpu_module_set_steer_one: frames; 0: every steered group takes three launches */
+static int32_t g_fwd_one;     /* mosrx_gpu_module_set_fwd_one: frames; 0: every forwarded group takes four launches */
 
 void mosrx_gpu_module_cfg_default(mosrx_gpu_module_cfg *cfg)
 {
@@ -216,6 +217,18 @@ int mosrx_gpu_module_set_steer_one(int32_t max_frames)
 }
 
 int32_t mosrx_gpu_module_get_steer_one(void) { return g_steer_one; }
+
+int mosrx_gpu_module_set_fwd_one(int32_t max_frames)
+{
+	if (max_frames < 0 || (uint32_t)max_frames > MOSRX_FWD_ONE_MAX)
+		return -EINVAL;
+	pthread_mutex_lock(&g_lock);
+	g_fwd_one = max_frames;
+	pthread_mutex_unlock(&g_lock);
+	return 0;
+}
+
+int32_t mosrx_gpu_module_get_fwd_one(void) { return g_fwd_one; }
 
 /* mosrx_gpu_module_set_fwd: the tables every context opened from now on gets,
  * and whether an end-host socket listens; g_fwd_on 0: forwarding off */
@@ -359,6 +372,17 @@ uint64_t mosrx_gpu_module_steer_one_count(struct mtcp_thread_context *ctx)
 	for (i = 0; pv && g_steer_one > 0 && i < g_cfg.num_ifs; i++)
 		if (pv->ifs[i].mc)
 			sum += mosrx_steer_one_count(pv->ifs[i].mc);
+	return sum;
+}
+
+uint64_t mosrx_gpu_module_fwd_one_count(struct mtcp_thread_context *ctx)
+{
+	struct gpu_priv *pv = priv_of(ctx);
+	uint64_t sum = 0;
+	uint32_t i;
+	for (i = 0; pv && g_fwd_one > 0 && i < g_cfg.num_ifs; i++)
+		if (pv->ifs[i].mc)
+			sum += mosrx_fwd_one_count(pv->ifs[i].mc);
 	return sum;
 }
 
@@ -670,6 +694,12 @@ static void gpu_init_handle(struct mtcp_thread_context *ctx)
 		 * by one launch (left at 0 the context is not touched: off is its default) */
 		if (g_steer_one && (rc = mosrx_set_steer_one(is->mc, (uint32_t)g_steer_one))) {
 			fprintf(stderr, "[mosrx] gpu_module: steer_one %d: %s\n", g_steer_one, mosrx_strerror(rc));
+			exit(EXIT_FAILURE);
+		}
+		/* mosrx_gpu_module_set_fwd_one: a forwarded group whose batches all fit is planned and
+		 * built by one launch (left at 0 the context is not touched) */
+		if (g_fwd_one && (rc = mosrx_set_fwd_one(is->mc, (uint32_t)g_fwd_one))) {
+			fprintf(stderr, "[mosrx] gpu_module: fwd_one %d: %s\n", g_fwd_one, mosrx_strerror(rc));
 			exit(EXIT_FAILURE);
 		}
 		/* mosrx_gpu_module_set_fwd: the context's tables; every group submit is then armed */

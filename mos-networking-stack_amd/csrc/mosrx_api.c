@@ -1293,6 +1293,32 @@ static int fwd_outputs(int device, const mosrx_batch *b, uint32_t nb, const mosr
 
 static void fwd_mark_used(mosrx_ctx *c);
 
+/* The plan and descriptor launches over a queue's or a group's two tables,
+ * whose largest batch has maxn frames: the one launch when the context's limit
+ * admits every batch (mosrx_set_fwd_one), else -- and always with the limit at
+ * 0 -- the four. */
+static int fwd_desc_queue_launch(mosrx_ctx *c, const mosrx_fqparams *fq, const mosrx_dqparams *dq, uint32_t maxn,
+                                 void *stream)
+{
+	mosrx_oparams op;
+	int rc;
+	if (!c->fwd_one || maxn > c->fwd_one)
+		return mosrx_launch_fwd_desc_queue(fq, dq, stream);
+	memset(&op, 0, sizeof(op));
+	op.fdesc = fq->desc;
+	op.ddesc = dq->desc;
+	op.tab = fq->tab;
+	op.nb = fq->nb;
+	op.rec_bytes = fq->rec_bytes;
+	op.forward = fq->forward;
+	op.num_msp = fq->num_msp;
+	op.listener = fq->listener;
+	op.nrings = fq->nrings;
+	if (!(rc = mosrx_launch_fwd_one(&op, stream)))
+		c->fwd_one_count++;
+	return rc;
+}
+
 /* The plan and descriptor launches of an armed group, behind its classify (and
  * steer) launches on the slot's stream: over the records and descriptors where
  * the classify launch wrote and read them (s->h_qdesc), into the caller's
@@ -1304,7 +1330,7 @@ static int group_fwd(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_
 {
 	mosrx_fqparams fq;
 	mosrx_dqparams dq;
-	uint32_t i, tiles = 0;
+	uint32_t i, tiles = 0, maxn = 0;
 	uint64_t pre = 0;
 	int rc;
 	for (i = 0; i < nb; pre += b[i].n, i++) {
@@ -1336,6 +1362,8 @@ static int group_fwd(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_
 		f->tile_base = d->tile_base = tiles;
 		d->pad = 0;
 		tiles += (b[i].n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+		if (b[i].n > maxn)
+			maxn = b[i].n;
 	}
 	HIPCHK(hipMemcpyAsync(s->d_fdesc, s->h_fdesc, nb * sizeof(mosrx_fdesc), hipMemcpyHostToDevice, s->stream));
 	HIPCHK(hipMemcpyAsync(s->d_ddesc, s->h_ddesc, nb * sizeof(mosrx_ddesc), hipMemcpyHostToDevice, s->stream));
@@ -1353,7 +1381,7 @@ static int group_fwd(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_
 	fq.nrings = dq.nrings = o->nrings;
 	dq.desc = s->d_ddesc;
 	fwd_mark_used(c);
-	if ((rc = mosrx_launch_fwd_desc_queue(&fq, &dq, (void *)s->stream)))
+	if ((rc = fwd_desc_queue_launch(c, &fq, &dq, maxn, (void *)s->stream)))
 		return rc;
 	for (i = 0, pre = 0; i < nb; pre += b[i].n, i++) {
 		const size_t n = b[i].n;
@@ -2055,6 +2083,11 @@ static int fwd_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, uint
 	return 0;
 }
 
+static int fwd_plan_desc_one(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, int in_ifidx,
+                             mosrx_fwd *d_plan, uint32_t nrings, uint32_t *d_tx_src, uint16_t *d_tx_len,
+                             uint32_t *d_tx_mac, mosrx_fwd_ring *d_rings, void *d_scratch, size_t scratch_bytes,
+                             hipStream_t s);
+
 /* One enqueue of operation `op` on batch b (see mosrx_time_op). */
 static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out, void *aux, hipStream_t s)
 {
@@ -2114,7 +2147,9 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 		uint32_t k = 0;
 		uint8_t *blk, *toff, *tsrc, *tlen, *tnif, *tcnt, *scr;
 		const size_t w = STEER_TMP_RND((size_t)c->fwd_tmp_n * 4);
-		int rc = mosrx_fwd_plan_dev(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, s);
+		/* the descriptor form under mosrx_set_fwd_one's limit: plan and rings in one launch, below */
+		const int one = op == MOSRX_OP_FWD_DESC && c->fwd_one && b->n <= c->fwd_one;
+		int rc = one ? 0 : mosrx_fwd_plan_dev(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, s);
 		if (rc || op == MOSRX_OP_FWD_PLAN)
 			return rc;
 		while (k < c->nxs && c->xs[k] != s)
@@ -2126,6 +2161,10 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 		tnif = tlen + STEER_TMP_RND((size_t)c->fwd_tmp_n * 2);
 		tcnt = tnif + STEER_TMP_RND(c->fwd_tmp_n);
 		scr = tcnt + 256;
+		if (one)
+			return fwd_plan_desc_one(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, c->fwd_tmp_rings, (uint32_t *)tsrc,
+			                         (uint16_t *)tlen, (uint32_t *)blk, (mosrx_fwd_ring *)tcnt, scr,
+			                         STEER_TMP_RND(mosrx_fwd_desc_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)), s);
 		if (op == MOSRX_OP_FWD_DESC)
 			return mosrx_fwd_desc_rings_dev(c, b, (const mosrx_fwd *)aux, c->fwd_tmp_rings, (uint32_t *)tsrc, (uint16_t *)tlen,
 			                                (uint32_t *)blk, (mosrx_fwd_ring *)tcnt, scr,
@@ -2461,6 +2500,7 @@ struct mosrx_queue {
 	 * parallel to d_fdesc; fwd_desc: attached (then fwd is set, fwd_build is not) */
 	mosrx_ddesc *d_ddesc;
 	int fwd_desc;
+	uint32_t fwd_maxn;   /*   its largest batch: what mosrx_set_fwd_one's limit is held against */
 };
 
 int mosrx_queue_create_ex(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, void *const *d_out,
@@ -2799,6 +2839,18 @@ int mosrx_set_steer_one(mosrx_ctx *c, uint32_t max_frames)
 uint32_t mosrx_get_steer_one(const mosrx_ctx *c) { return c ? c->steer_one : 0; }
 
 uint64_t mosrx_steer_one_count(const mosrx_ctx *c) { return c ? c->steer_one_count : 0; }
+
+int mosrx_set_fwd_one(mosrx_ctx *c, uint32_t max_frames)
+{
+	if (!c || max_frames > MOSRX_FWD_ONE_MAX)
+		return -EINVAL;
+	c->fwd_one = max_frames;
+	return 0;
+}
+
+uint32_t mosrx_get_fwd_one(const mosrx_ctx *c) { return c ? c->fwd_one : 0; }
+
+uint64_t mosrx_fwd_one_count(const mosrx_ctx *c) { return c ? c->fwd_one_count : 0; }
 
 int mosrx_steer_dev(mosrx_ctx *c, const void *d_rec, uint32_t n, int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart,
                     void *d_scratch, size_t scratch_bytes, void *stream)
@@ -3198,7 +3250,7 @@ static int queue_fwd(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 		dq.nb = fq.nb;
 		dq.total_tiles = fq.total_tiles;
 		dq.nrings = fq.nrings;
-		rc = mosrx_launch_fwd_desc_queue(&fq, &dq, (void *)s);
+		rc = fwd_desc_queue_launch(c, &fq, &dq, q->fwd_maxn, (void *)s);
 	} else
 		rc = mosrx_launch_fwd_queue(&fq, q->fwd_build, (void *)s);
 	mosrx__note_stream(c, s);   /* (after the launches: its event covers them) */
@@ -3306,6 +3358,40 @@ size_t mosrx_fwd_desc_scratch_bytes(uint32_t n, uint32_t nrings)
 	return mosrx_fwd_rings_scratch_bytes(n, nrings);
 }
 
+/* The one launch over the single batch in dp (n <= MOSRX_FWD_ONE_MAX); with fp,
+ * the plan first, from its records, length array, in_ifidx and record size. */
+static int fwd_one_batch(mosrx_ctx *c, const mosrx_dparams *dp, const mosrx_fparams *fp, hipStream_t s)
+{
+	mosrx_oparams op;
+	int rc;
+	memset(&op, 0, sizeof(op));
+	op.tab = dp->tab;
+	op.nb = 1;
+	op.nrings = dp->nrings;
+	op.oned.frames = dp->frames;
+	op.oned.off = dp->off;
+	op.oned.plan = dp->plan;
+	op.oned.tx_src = dp->tx_src;
+	op.oned.tx_len = dp->tx_len;
+	op.oned.tx_mac = dp->tx_mac;
+	op.oned.rings = dp->rings;
+	op.oned.frames_bytes = dp->frames_bytes;
+	op.oned.n = dp->n;
+	if (fp) {
+		op.rec_bytes = fp->rec_bytes;
+		op.forward = c->params.forward;
+		op.num_msp = c->params.num_msp;
+		op.listener = c->fwd_listener;
+		op.onef.len = fp->len;
+		op.onef.rec = fp->rec;
+		op.onef.plan = (mosrx_fwd *)dp->plan;
+		op.onef.in_ifidx = (uint32_t)fp->in_ifidx;
+	}
+	if (!(rc = mosrx_launch_fwd_one(&op, (void *)s)))
+		c->fwd_one_count++;
+	return rc;
+}
+
 int mosrx_fwd_desc_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint32_t nrings,
                              uint32_t *d_tx_src, uint16_t *d_tx_len, uint32_t *d_tx_mac, mosrx_fwd_ring *d_rings,
                              void *d_scratch, size_t scratch_bytes, void *stream)
@@ -3342,7 +3428,57 @@ int mosrx_fwd_desc_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd
 	s = stream ? (hipStream_t)stream : c->stream;
 	HIPCHK(hipSetDevice(c->device));
 	fwd_mark_used(c);
-	rc = mosrx_launch_fwd_desc(&dp, (void *)s);
+	if (c->fwd_one && b->n <= c->fwd_one)
+		rc = fwd_one_batch(c, &dp, NULL, s);   /* (the scratch is left as it is) */
+	else
+		rc = mosrx_launch_fwd_desc(&dp, (void *)s);
+	mosrx__note_stream(c, s);
+	return rc;
+}
+
+/* MOSRX_OP_FWD_DESC under mosrx_set_fwd_one's limit: mosrx_fwd_plan_dev and
+ * mosrx_fwd_desc_rings_dev on one batch, their refusals in their order, as one
+ * launch. */
+static int fwd_plan_desc_one(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, int in_ifidx,
+                             mosrx_fwd *d_plan, uint32_t nrings, uint32_t *d_tx_src, uint16_t *d_tx_len,
+                             uint32_t *d_tx_mac, mosrx_fwd_ring *d_rings, void *d_scratch, size_t scratch_bytes,
+                             hipStream_t s)
+{
+	mosrx_fparams fp;
+	mosrx_dparams dp;
+	int rc;
+	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || (rec_bytes != 8 && rec_bytes != 16) || in_ifidx < 0 ||
+	    in_ifidx >= MOSRX_FWD_MAX_NETDEVS || (b->n && (!d_rec || ((uintptr_t)d_rec & (uintptr_t)(rec_bytes - 1)))))
+		return -EINVAL;
+	if ((rc = fwd_batch(c, b, &fp)))
+		return rc;
+	if (!c->d_fwd)
+		return -ENOENT;
+	if (!d_tx_src || ((uintptr_t)d_tx_src & 3) || !d_tx_len || ((uintptr_t)d_tx_len & 1) || !d_tx_mac ||
+	    ((uintptr_t)d_tx_mac & 3) || !d_rings || ((uintptr_t)d_rings & 15) || !d_scratch || ((uintptr_t)d_scratch & 15) ||
+	    nrings < 1 || nrings > MOSRX_FWD_MAX_NETDEVS || scratch_bytes < mosrx_fwd_desc_scratch_bytes(b->n, nrings) ||
+	    nrings < c->fwd_num_netdevs)
+		return -EINVAL;
+	if (!s)
+		s = c->stream;
+	fp.rec = (const uint8_t *)d_rec;
+	fp.rec_bytes = (uint32_t)rec_bytes;
+	fp.in_ifidx = in_ifidx;
+	memset(&dp, 0, sizeof(dp));
+	dp.frames = fp.frames;
+	dp.off = fp.off;
+	dp.tab = fp.tab;
+	dp.plan = d_plan;
+	dp.frames_bytes = fp.frames_bytes;
+	dp.n = fp.n;
+	dp.nrings = nrings;
+	dp.tx_src = d_tx_src;
+	dp.tx_len = d_tx_len;
+	dp.tx_mac = d_tx_mac;
+	dp.rings = d_rings;
+	HIPCHK(hipSetDevice(c->device));
+	fwd_mark_used(c);
+	rc = fwd_one_batch(c, &dp, &fp, s);
 	mosrx__note_stream(c, s);
 	return rc;
 }
@@ -3351,7 +3487,7 @@ int mosrx_queue_set_fwd_desc(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd
 {
 	mosrx_fdesc *h;
 	mosrx_ddesc *g;
-	uint32_t i, tiles = 0;
+	uint32_t i, tiles = 0, maxn = 0;
 	size_t rows;
 	if (!c || !q)
 		return -EINVAL;
@@ -3391,6 +3527,8 @@ int mosrx_queue_set_fwd_desc(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd
 		h[i].in_ifidx = f->in_ifidx ? f->in_ifidx[i] : 0;
 		h[i].rings = g[i].rings = f->d_rings[i];
 		tiles += (d->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
+		if (d->n > maxn)
+			maxn = d->n;
 		if (!d->n)
 			continue;
 		h[i].frames = g[i].frames = d->frames;
@@ -3441,6 +3579,7 @@ int mosrx_queue_set_fwd_desc(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd
 	q->fwd_tiles = tiles;
 	q->fwd_nrings = f->nrings;
 	q->fwd_cap_units = 0;
+	q->fwd_maxn = maxn;
 	q->fwd_desc = 1;
 	q->fwd = 1;
 	return 0;

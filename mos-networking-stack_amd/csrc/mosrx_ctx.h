@@ -169,6 +169,8 @@ struct mosrx_ctx {
 	uint32_t fwd_pool_next;
 	uint32_t fwd_listener;           /* mosrx_fwd_set_listener */
 	uint32_t fwd_num_netdevs;        /* the installed tables' num_netdevs (the ring build's least nrings) */
+	uint32_t fwd_one;                /* batches of at most this many frames are planned and built in one launch (mosrx_set_fwd_one); 0: off */
+	uint64_t fwd_one_count;          /*   forwarding launches that were */
 	/* MOSRX_OP_FWD's / MOSRX_OP_FWD_RINGS' own TX outputs + scratch, one block of
 	 * fwd_tmp_stride bytes per timing stream and one for the context stream
 	 * (mosrx_time_op); fwd_tmp_rings rings of fwd_tmp_cap bytes (MOSRX_OP_FWD: 1) */

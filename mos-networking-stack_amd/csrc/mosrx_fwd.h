@@ -197,6 +197,37 @@ _Static_assert(sizeof(mosrx_ddesc) == 72 && sizeof(mosrx_dqparams) == 40, "descr
  * is not looked at.  A queue of empty batches launches the scan alone. */
 int mosrx_launch_fwd_desc_queue(const mosrx_fqparams *fq, const mosrx_dqparams *dq, void *stream);
 
+/* The one-launch form (mosrx_set_fwd_one): the plan and the descriptor rings of
+ * every batch by one workgroup per batch, the same bytes as the four launches
+ * above (no scratch is read or written).  The batches are the queue form's two
+ * tables as they are (tile_base is not looked at), or, with ddesc NULL, the one
+ * batch in onef / oned (nb = 1).  rec_bytes 0: no plan -- the records are read
+ * from ddesc[].plan, fdesc and onef are not looked at, and the launch is
+ * mosrx_launch_fwd_desc's three.  Every batch has n <= MOSRX_FWD_ONE_MAX: the
+ * caller's to see to for a table (a workgroup stops after that many frames). */
+typedef struct mosrx_oparams {
+	const mosrx_fdesc   *fdesc;  /* nb, device-resident: frames' len, rec, in_ifidx and the plan to write */
+	const mosrx_ddesc   *ddesc;  /* nb, device-resident; NULL: onef / oned */
+	const mosrx_fwd_dev *tab;
+	uint32_t nb;
+	uint32_t rec_bytes;          /* 8 or 16: plan first; 0: the plan is there */
+	int32_t  forward;            /* mosrx_mos_forwards' parameters */
+	uint32_t num_msp, listener;
+	uint32_t nrings;             /* 1 .. MOSRX_FWD_MAX_NETDEVS */
+	mosrx_fdesc onef;
+	mosrx_ddesc oned;
+} mosrx_oparams;
+
+#ifdef __cplusplus
+static_assert(sizeof(mosrx_oparams) == 216, "one-launch form: 216-byte parameters");
+#else
+_Static_assert(sizeof(mosrx_oparams) == 216, "one-launch form: 216-byte parameters");
+#endif
+
+/* One launch of nb workgroups on `stream`; 0, -EINVAL or -EIO.  Allocates
+ * nothing.  An empty batch's workgroup writes its zeroed rings and nothing else. */
+int mosrx_launch_fwd_one(const mosrx_oparams *op, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

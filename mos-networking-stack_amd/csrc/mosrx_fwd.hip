@@ -77,108 +77,13 @@ __device__ __forceinline__ void fwd_plan_body(const mosrx_fparams p, uint32_t bl
 	__shared__ int32_t s_rp[MOSRX_FWD_MAX_ROUTES], s_rn[MOSRX_FWD_MAX_ROUTES];
 	__shared__ uint32_t s_am[MOSRX_FWD_MAX_ARP], s_av[MOSRX_FWD_MAX_ARP];
 	__shared__ int32_t s_ap[MOSRX_FWD_MAX_ARP];
-	const mosrx_fwd_dev *T = p.tab;
 	const uint32_t t = threadIdx.x, i = blk * MOSRX_FWD_THREADS + t;
-	const uint32_t nr = min(T->num_routes, (uint32_t)MOSRX_FWD_MAX_ROUTES);
-	const uint32_t na = min(T->num_arp, (uint32_t)MOSRX_FWD_MAX_ARP);
-	// nic_forward_table[in_ifidx], -1 without a table: uniform over the batch
-	const int32_t nicout = T->has_nic_fwd ? (int32_t)T->nic_fwd[p.in_ifidx & (MOSRX_FWD_MAX_NETDEVS - 1)] : -1;
-	const bool walk = nicout == -1;   // else ForwardIPPacket's fast path: no table is read
-	if (walk) {
-		for (uint32_t j = t; j < nr; j += MOSRX_FWD_THREADS) {
-			s_rm[j] = T->r_mask[j];
-			s_rv[j] = T->r_masked[j];
-			s_rp[j] = T->r_prefix[j];
-			s_rn[j] = T->r_nif[j];
-		}
-		for (uint32_t j = t; j < na; j += MOSRX_FWD_THREADS) {
-			s_am[j] = T->a_mask[j];
-			s_av[j] = T->a_masked[j];
-			s_ap[j] = T->a_prefix[j];
-		}
-	}
-	__syncthreads();
+#define FWD_PLAN 1
+#include "mosrx_fwd_plan_body.inc"
 	if (i >= p.n)
 		return;
-	const uint32_t reason = *reinterpret_cast<const uint32_t *>(p.rec + (uint64_t)i * RB + (RB - 4u)) & 0xFFu;
-	const uint32_t o = p.off[i];
-	const uint32_t cap = eff_caplen(o, p.len[i], p.frames_bytes);
-	const __amdgpu_buffer_rsrc_t rs = frame_rsrc(p.frames, p.frames_bytes);
-	const uint32_t w_len = fwd_ld32(rs, o + 16u);     // iph->tot_len (network order) in the low half
-	const uint32_t daddr = fwd_ld32(rs, o + 30u);     // iph->daddr as mOS loads it
-	const uint32_t ip_len = ((w_len & 0xFFu) << 8) | ((w_len >> 8) & 0xFFu);
-	// mosrx_mos_forwards (csrc/rx_loop.c)
-	const uint32_t bit = 1u << reason;
-	const uint32_t m_msp = (1u << MOSRX_R_NON_IPV4) | (1u << MOSRX_R_ARP) | (1u << MOSRX_R_NOT_TCP) |
-	                       (1u << MOSRX_R_TCP_BADCSUM);
-	const uint32_t m_tcp = (1u << MOSRX_R_TCP_OK) | (1u << MOSRX_R_TCP_LEN_OK);
-	bool fwd = false;
-	if (reason < MOSRX_R_COUNT)
-		fwd = (bit & m_msp) ? p.num_msp != 0
-		    : (bit & m_tcp) ? (p.num_msp != 0 && !p.listener)
-		    : reason == MOSRX_R_NOVERIFY_PASS;
-	fwd = fwd && p.forward;
-	const bool eth = reason == MOSRX_R_NON_IPV4 || reason == MOSRX_R_ARP;
-	// an IPv4 frame whose packet does not lie inside the capture is TRUNCATED or
-	// IP_SHORT to the classify kernels: never forwarded, whatever the record says
-	const bool ip_ok = cap >= 34u && ip_len >= 20u && 14u + ip_len <= cap;
-
-	// GetOutputInterface: from prefix -1, strictly greater wins
-	int32_t best = -1, nif = -1;
-	// GetDestinationHWaddr: from prefix 0; a prefix-1 entry matches its exact
-	// address, ends the walk and overrides what was found before it
-	int32_t abest = 0;
-	uint32_t aidx = 0xFFFFu;
-	if (walk) {
-		for (uint32_t j = 0; j < nr; j++) {
-			const int32_t pf = s_rp[j];
-			if ((daddr & s_rm[j]) == s_rv[j] && pf > best) {
-				best = pf;
-				nif = s_rn[j];
-			}
-		}
-		bool done = false;
-		for (uint32_t j = 0; j < na; j++) {
-			const int32_t pf = s_ap[j];
-			const bool m = (daddr & s_am[j]) == s_av[j];
-			const bool take = !done && m && (pf == 1 || pf > abest);
-			if (take) {
-				aidx = j;
-				abest = pf == 1 ? abest : pf;
-				done = pf == 1;
-			}
-		}
-	}
-	uint32_t kind = MOSRX_FWD_NONE, tx_len = 0, arp = 0xFFFFu;
-	int32_t oif = -1;
-	if (fwd && eth && cap >= 14u) {
-		if (nicout == -1)
-			kind = MOSRX_FWD_NO_NIC;
-		else {
-			kind = MOSRX_FWD_ETH;
-			tx_len = cap;
-			oif = nicout;
-		}
-	} else if (fwd && !eth && ip_ok) {
-		if (!walk) {
-			kind = MOSRX_FWD_IP;
-			oif = nicout;
-		} else if (nif < 0)
-			kind = MOSRX_FWD_NO_ROUTE;
-		else if (aidx == 0xFFFFu) {
-			kind = MOSRX_FWD_NO_ARP;
-			oif = nif;
-		} else {
-			kind = MOSRX_FWD_IP;
-			oif = nif;
-			arp = aidx;
-		}
-		if (kind == MOSRX_FWD_IP)
-			tx_len = 14u + ip_len;
-	}
-	u32x2 v;
-	v.x = tx_len | (((uint32_t)oif & 0xFFu) << 16) | (kind << 24);
-	v.y = arp;
+#define FWD_PLAN 2
+#include "mosrx_fwd_plan_body.inc"
 	*reinterpret_cast<u32x2 *>(p.plan + i) = v;
 }
 
@@ -653,32 +558,7 @@ __device__ __forceinline__ void fwd_desc_store_body(const mosrx_dparams &p, uint
 		base = p.scratch[4u * ((uint64_t)blk * nrings + q) + 2u];
 	const uint32_t j = base + rank;
 	if (sent && j < p.n) {
-		// bytes 0 .. 11 of the frame the byte-ring copy writes (its r == 0 unit)
-		const __amdgpu_buffer_rsrc_t rs = frame_rsrc(p.frames, p.frames_bytes);
-		const mosrx_fwd_dev *T = p.tab;
-		const u32x4 h = fwd_ld128(rs, o);
-		u32x3 m = {h.x, h.y, h.z};
-		if ((pl.x >> 24) == MOSRX_FWD_IP) {
-			const uint32_t ai = pl.y & 0xFFFFu;
-			const uint32_t nif = q & (MOSRX_FWD_MAX_NETDEVS - 1u);
-			const uint32_t *sm = reinterpret_cast<const uint32_t *>(T->netdev_haddr[nif]);
-			const uint32_t s0 = sm[0], s1 = sm[1] & 0xFFFFu;
-			uint32_t d0 = h.x, d1 = h.y & 0xFFFFu;   // the frame's own h_dest (nic_forward_table path)
-			if (ai < MOSRX_FWD_MAX_ARP) {
-				const uint32_t *dm = reinterpret_cast<const uint32_t *>(T->a_haddr[ai]);
-				d0 = dm[0];
-				d1 = dm[1] & 0xFFFFu;
-			}
-			m.x = d0;
-			m.y = d1 | (s0 << 16);
-			m.z = (s0 >> 16) | (s1 << 16);
-		}
-		p.tx_src[j] = i;
-		p.tx_len[j] = (uint16_t)(pl.x & 0xFFFFu);
-		uint32_t *mac = p.tx_mac + 3u * (uint64_t)j;
-		mac[0] = m.x;
-		mac[1] = m.y;
-		mac[2] = m.z;
+#include "mosrx_fwd_desc_entry.inc"
 	}
 	if (t < nrings) {
 		uint32_t tu = 0, tc = 0;
@@ -730,6 +610,174 @@ __global__ __launch_bounds__(MOSRX_FWD_THREADS) void mosrx_fwd_desc_store_queue_
 	p.rings = d.rings;
 	p.scratch = dq.scratch + 4u * ((uint64_t)d.tile_base * min(dq.nrings, FWD_NQ));
 	fwd_desc_store_body(p, blockIdx.x - d.tile_base);
+}
+
+// ---- plan + descriptor rings, one launch --------------------------------------
+// For batches of a tile or so the four launches above are launch latency and
+// little else.  Here one workgroup owns a batch and walks it in tiles of
+// MOSRX_FWD_TILE frames, lane t owning frame tile * 256 + t throughout:
+//   1. per tile  the frame's plan record (PLAN: made as fwd_plan_body makes it
+//                and stored; else loaded), its netdev, units and rank among the
+//                tile's frames of that netdev (the same masked scan); the rank
+//                kept in LDS (a byte: < 256), the tile's sent frames and units
+//                per netdev in s_tc / s_tu
+//   2. once      lane q < nrings turns column q of s_tc into the sent frames of
+//                the earlier tiles; rings[q] = {start, count, 0, units} stored
+//                whole -- the workgroup owns the batch, so no atomics
+//   3. per tile  entry = start + earlier tiles' + rank; the entry stored by the
+//                frame's own lane as fwd_desc_store_body stores it
+// Phase 3 walks the tiles backwards: the last tile's record, offset and rank
+// are still in registers, so a one-tile batch reads nothing twice.  An earlier
+// tile's record is re-read from plan[] by the lane that stored it, its rank from
+// the byte the same lane wrote.  Every loop's bound (the tiles, <= 32; nrings,
+// <= 16; the table sizes) is known at entry, every barrier sits outside lane-
+// dependent control flow, and no workgroup waits on another.
+#define FWD_ONE_TILES (MOSRX_FWD_ONE_MAX / MOSRX_FWD_TILE)
+static_assert(MOSRX_FWD_ONE_MAX % MOSRX_FWD_TILE == 0 && FWD_ONE_TILES == 32u, "one workgroup walks at most 32 tiles");
+
+// Phase 1's share of tile k once its lanes hold their records: netdev, units and
+// rank of this lane's frame (the rank also into its byte of s_rank), the tile's
+// totals per netdev into row k.  Ends in a barrier: the next tile's scan
+// rewrites s_wu / s_wc.
+__device__ __forceinline__ void fwd_one_tile_totals(u32x2 pl, uint32_t k, uint32_t nrings, uint32_t (*s_wu)[FWD_NQ],
+                                                    uint32_t (*s_wc)[FWD_NQ], uint32_t (*s_tu)[FWD_NQ],
+                                                    uint32_t (*s_tc)[FWD_NQ], uint8_t *s_rank, uint32_t &q,
+                                                    uint32_t &units, uint32_t &rank)
+{
+	const uint32_t t = threadIdx.x;
+	uint32_t excl;
+	units = fwd_ring_units(pl, nrings, q);
+	fwd_ring_tile_scan(q, units, nrings, s_wu, s_wc, excl, rank);
+	s_rank[k * MOSRX_FWD_TILE + t] = (uint8_t)rank;
+	if (t < nrings) {
+		uint32_t tu = 0, tc = 0;
+#pragma unroll
+		for (uint32_t w = 0; w < FWD_WAVES; w++) {
+			tu += s_wu[w][t];
+			tc += s_wc[w][t];
+		}
+		s_tu[k][t] = tu;
+		s_tc[k][t] = tc;
+	}
+	__syncthreads();
+}
+
+template <uint32_t RB, bool PLAN>
+__global__ __launch_bounds__(MOSRX_FWD_THREADS) void mosrx_fwd_one_kernel(mosrx_oparams op)
+{
+	__shared__ uint32_t s_rm[MOSRX_FWD_MAX_ROUTES], s_rv[MOSRX_FWD_MAX_ROUTES];
+	__shared__ int32_t s_rp[MOSRX_FWD_MAX_ROUTES], s_rn[MOSRX_FWD_MAX_ROUTES];
+	__shared__ uint32_t s_am[MOSRX_FWD_MAX_ARP], s_av[MOSRX_FWD_MAX_ARP];
+	__shared__ int32_t s_ap[MOSRX_FWD_MAX_ARP];
+	__shared__ uint32_t s_wu[FWD_WAVES][FWD_NQ], s_wc[FWD_WAVES][FWD_NQ];
+	__shared__ uint32_t s_tu[FWD_ONE_TILES][FWD_NQ], s_tc[FWD_ONE_TILES][FWD_NQ];
+	__shared__ uint32_t s_tot[FWD_NQ], s_start[FWD_NQ];
+	__shared__ uint8_t s_rank[MOSRX_FWD_ONE_MAX];
+	if (blockIdx.x >= op.nb)
+		return;
+	const mosrx_ddesc d = op.ddesc ? op.ddesc[blockIdx.x] : op.oned;
+	const uint32_t nrings = min(op.nrings, FWD_NQ);
+	const uint32_t t = threadIdx.x;
+	const uint32_t tiles = min((d.n + MOSRX_FWD_TILE - 1u) / MOSRX_FWD_TILE, FWD_ONE_TILES);
+	mosrx_dparams p = {};   // as the store launch's body takes the batch
+	p.frames = d.frames;
+	p.off = d.off;
+	p.tab = op.tab;
+	p.plan = d.plan;
+	p.frames_bytes = d.frames_bytes;
+	p.n = d.n;
+	p.tx_src = d.tx_src;
+	p.tx_len = d.tx_len;
+	p.tx_mac = d.tx_mac;
+	mosrx_fparams fp = {};  // as the plan launch's body takes it
+	if constexpr (PLAN) {
+		const mosrx_fdesc f = op.fdesc ? op.fdesc[blockIdx.x] : op.onef;
+		fp.frames = d.frames;
+		fp.off = d.off;
+		fp.len = f.len;
+		fp.rec = f.rec;
+		fp.tab = op.tab;
+		fp.plan = f.plan;
+		fp.frames_bytes = d.frames_bytes;
+		fp.n = d.n;
+		fp.in_ifidx = (int32_t)f.in_ifidx;
+		fp.forward = op.forward;
+		fp.num_msp = op.num_msp;
+		fp.listener = op.listener;
+	}
+	u32x2 pl = {0u, 0u};
+	uint32_t fo = 0, q = 0, units = 0, rank = 0;
+	if constexpr (PLAN) {
+		const mosrx_fparams &p = fp;
+#define FWD_PLAN 1
+#include "mosrx_fwd_plan_body.inc"
+		for (uint32_t k = 0; k < tiles; k++) {
+			const uint32_t i = k * MOSRX_FWD_TILE + t;
+			pl.x = pl.y = 0u;
+			fo = 0;
+			if (i < p.n) {
+#define FWD_PLAN 2
+#include "mosrx_fwd_plan_body.inc"
+				*reinterpret_cast<u32x2 *>(p.plan + i) = v;
+				pl = v;
+				fo = o;
+			}
+			fwd_one_tile_totals(pl, k, nrings, s_wu, s_wc, s_tu, s_tc, s_rank, q, units, rank);
+		}
+	} else {
+		for (uint32_t k = 0; k < tiles; k++) {
+			const uint32_t i = k * MOSRX_FWD_TILE + t;
+			pl.x = pl.y = 0u;
+			fo = 0;
+			if (i < p.n) {
+				pl = *reinterpret_cast<const u32x2 *>(p.plan + i);
+				fo = p.off[i];
+			}
+			fwd_one_tile_totals(pl, k, nrings, s_wu, s_wc, s_tu, s_tc, s_rank, q, units, rank);
+		}
+	}
+	// 2. lane q: its column's exclusive prefix over the tiles, its ring's row
+	uint32_t cnt = 0, un = 0;
+	if (t < nrings) {
+		for (uint32_t k = 0; k < tiles; k++) {
+			const uint32_t c = s_tc[k][t];
+			s_tc[k][t] = cnt;
+			cnt += c;
+			un += s_tu[k][t];
+		}
+		s_tot[t] = cnt;
+	}
+	__syncthreads();
+	if (t < nrings) {
+		uint32_t start = 0;
+		for (uint32_t g = 0; g < nrings; g++)
+			start += g < t ? s_tot[g] : 0u;
+		s_start[t] = start;
+		u32x4 row = {start, cnt, 0u, un};
+		*reinterpret_cast<u32x4 *>(d.rings + t) = row;
+	}
+	__syncthreads();
+	// 3. the entries, last tile first
+	for (uint32_t k = tiles; k-- > 0u;) {
+		const uint32_t i = k * MOSRX_FWD_TILE + t;
+		if (k + 1u != tiles) {
+			pl.x = pl.y = 0u;
+			fo = 0;
+			if (i < p.n) {
+				pl = *reinterpret_cast<const u32x2 *>(p.plan + i);
+				fo = p.off[i];
+			}
+			units = fwd_ring_units(pl, nrings, q);
+			rank = s_rank[i];
+		}
+		const bool sent = units != 0u;   // (then q < nrings and i < n)
+		const uint32_t qq = q & (FWD_NQ - 1u);
+		const uint32_t j = s_start[qq] + s_tc[k][qq] + rank;
+		if (sent && j < p.n) {
+			const uint32_t o = fo;
+#include "mosrx_fwd_desc_entry.inc"
+		}
+	}
 }
 
 static int fwd_common_ok(const mosrx_fparams *fp)
@@ -866,5 +914,34 @@ extern "C" int mosrx_launch_fwd_desc_queue(const mosrx_fqparams *fq, const mosrx
 	hipLaunchKernelGGL(mosrx_fwd_ring_scan_queue_kernel, dim3(fq->nb), dim3(FWD_SCAN_THREADS), 0, s, *fq);
 	if (fq->total_tiles)
 		hipLaunchKernelGGL(mosrx_fwd_desc_store_queue_kernel, grid, block, 0, s, *dq);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+extern "C" int mosrx_launch_fwd_one(const mosrx_oparams *op, void *stream)
+{
+	const hipStream_t s = (hipStream_t)stream;
+	if (!op || !op->tab || op->nb == 0 || (op->rec_bytes != 0u && op->rec_bytes != 8u && op->rec_bytes != 16u) ||
+	    op->nrings < 1u || op->nrings > FWD_NQ || (op->ddesc && op->rec_bytes && !op->fdesc))
+		return -EINVAL;
+	if (!op->ddesc) {
+		const mosrx_ddesc *d = &op->oned;
+		const mosrx_fdesc *f = &op->onef;
+		if (op->nb != 1u || d->n > MOSRX_FWD_ONE_MAX || !d->rings || ((uintptr_t)d->rings & 15) ||
+		    (d->n && (!d->frames || !d->off || ((uintptr_t)d->off & 3) || !d->plan || ((uintptr_t)d->plan & 7) ||
+		              !d->tx_src || ((uintptr_t)d->tx_src & 3) || !d->tx_len || ((uintptr_t)d->tx_len & 1) ||
+		              !d->tx_mac || ((uintptr_t)d->tx_mac & 3))))
+			return -EINVAL;
+		if (op->rec_bytes && (f->in_ifidx >= MOSRX_FWD_MAX_NETDEVS ||
+		                      (d->n && (f->plan != d->plan || !f->len || ((uintptr_t)f->len & 1) || !f->rec ||
+		                                ((uintptr_t)f->rec & (op->rec_bytes - 1u))))))
+			return -EINVAL;
+	}
+	const dim3 grid(op->nb), block(MOSRX_FWD_THREADS);
+	if (op->rec_bytes == 0u)
+		hipLaunchKernelGGL((mosrx_fwd_one_kernel<8u, false>), grid, block, 0, s, *op);
+	else if (op->rec_bytes == 8u)
+		hipLaunchKernelGGL((mosrx_fwd_one_kernel<8u, true>), grid, block, 0, s, *op);
+	else
+		hipLaunchKernelGGL((mosrx_fwd_one_kernel<16u, true>), grid, block, 0, s, *op);
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }

@@ -110,6 +110,7 @@ OP_STEER_GATHER_SIDE = 9   # MOSRX_OP_STEER_GATHER_SIDE: ... in its side form (a
 SIDE_FHASH, SIDE_MATCH, SIDE_TCPINFO = 1, 2, 4   # MOSRX_SIDE_*
 STEER_QSLOTS = 257     # MOSRX_STEER_QSLOTS: qstart entries per batch
 STEER_ONE_MAX = 65536  # MOSRX_STEER_ONE_MAX: the most frames per batch the one-launch steer form takes
+FWD_ONE_MAX = 8192     # MOSRX_FWD_ONE_MAX: the most frames per batch the one-launch forwarding form takes
 # include/mosrx.h mosrx_tx_check: the TX checks of a frame, the frame untouched
 TX_CHECK_DTYPE = np.dtype([("ip_check", "<u2"), ("tcp_check", "<u2"), ("what", "u1"), ("ihl", "u1"),
                            ("pad", "<u2")])
@@ -487,6 +488,12 @@ def lib():
             "mosrx_gpu_module_steer_one_count": (U64, [P]),
             "mosrx_gpu_module_set_steer_one": (I, [C.c_int32]),
             "mosrx_gpu_module_get_steer_one": (C.c_int32, []),
+            "mosrx_set_fwd_one": (I, [P, U32]),
+            "mosrx_get_fwd_one": (U32, [P]),
+            "mosrx_fwd_one_count": (U64, [P]),
+            "mosrx_gpu_module_fwd_one_count": (U64, [P]),
+            "mosrx_gpu_module_set_fwd_one": (I, [C.c_int32]),
+            "mosrx_gpu_module_get_fwd_one": (C.c_int32, []),
             "mosrx_fwd_set": (I, [P, C.POINTER(FwdTables)]),
             "mosrx_fwd_set_listener": (I, [P, I]),
             "mosrx_fwd_plan_dev": (I, [P, C.POINTER(Batch), P, I, I, P, P]),
@@ -1147,6 +1154,19 @@ class Context:
         """mosrx_steer_one_count: this context's steer launches that took the one-launch form."""
         return int(lib().mosrx_steer_one_count(self.handle))
 
+    def set_fwd_one(self, max_frames: int) -> None:
+        """mosrx_set_fwd_one: forwarding launches whose batches all have at most max_frames
+        frames (up to FWD_ONE_MAX) plan and build their descriptor rings in one kernel; 0: the
+        four launches."""
+        _chk(lib().mosrx_set_fwd_one(self.handle, int(max_frames)), "mosrx_set_fwd_one")
+
+    def get_fwd_one(self) -> int:
+        return int(lib().mosrx_get_fwd_one(self.handle))
+
+    def fwd_one_count(self) -> int:
+        """mosrx_fwd_one_count: this context's forwarding launches that took the one-launch form."""
+        return int(lib().mosrx_fwd_one_count(self.handle))
+
     def slot_direct(self, slot: int) -> bool:
         """mosrx_slot_direct: the slot's last group submit ran copy-free."""
         rc = lib().mosrx_slot_direct(self.handle, slot)
@@ -1467,7 +1487,7 @@ class GpuBackend:
                  timing: bool = False, flowhash: bool = False, tx_csum: bool = False, compact: bool = False,
                  group_bytes: int = 0, group_max_us: int = 0, direct_kb: int | None = None,
                  direct_frames: int | None = None, module_lib=None, steer: bool | int = False,
-                 steer_one: int = 0, fwd: FwdTables | None = None, fwd_listener: bool = False):
+                 steer_one: int = 0, fwd: FwdTables | None = None, fwd_listener: bool = False, fwd_one: int = 0):
         self.L = L = module_lib or lib()
         cfg = ModuleCfg()
         L.mosrx_gpu_module_cfg_default(C.byref(cfg))
@@ -1501,6 +1521,8 @@ class GpuBackend:
         # steered groups of batches up to this many frames: one steer launch (0: never; always set,
         # so a backend does not inherit an earlier one's)
         _chk(L.mosrx_gpu_module_set_steer_one(int(steer_one)), "mosrx_gpu_module_set_steer_one")
+        # forwarded groups of batches up to this many frames: one forwarding launch (0: never; always set)
+        _chk(L.mosrx_gpu_module_set_fwd_one(int(fwd_one)), "mosrx_gpu_module_set_fwd_one")
         # forwarding on the GPU with these tables (None: off; always set, for the same reason)
         L.mosrx_gpu_module_set_fwd.restype = C.c_int
         L.mosrx_gpu_module_set_fwd.argtypes = [C.POINTER(FwdTables), C.c_int]
@@ -1525,6 +1547,12 @@ class GpuBackend:
     def steer_one_count(self) -> int:
         """mosrx_gpu_module_steer_one_count: steered groups that took the one-launch form."""
         return int(self.L.mosrx_gpu_module_steer_one_count(self.ctx))
+
+    def fwd_one_count(self) -> int:
+        """mosrx_gpu_module_fwd_one_count: forwarded groups that took the one-launch form."""
+        self.L.mosrx_gpu_module_fwd_one_count.restype = C.c_uint64
+        self.L.mosrx_gpu_module_fwd_one_count.argtypes = [C.c_void_p]
+        return int(self.L.mosrx_gpu_module_fwd_one_count(self.ctx))
 
     def recv_pkts(self, ifidx: int = 0) -> int:
         return self._recv(self.ctx, ifidx)
