@@ -218,8 +218,18 @@ def random_sets(seed, nsets=2):
     return [[(random_program(rng, rng.randint(2, 48)), b % 2) for b in range(32)] for _ in range(nsets)]
 
 
+def ret_a_sets(seed, nsets=2):
+    """The same programs with the final `ret #k` replaced by `ret a`: whether a
+    program that runs to its end matches then depends on the arithmetic before it."""
+    sets = random_sets(seed, nsets)
+    for ps in sets:
+        for p, _ in ps:
+            p[-1] = I_(0x16)
+    return sets
+
+
 def test_random_programs_admitted_and_compiled():
-    for ps in random_sets(7):
+    for ps in random_sets(7) + ret_a_sets(7):
         for p, _ in ps:
             assert mosrx.bpf_check(p) == 0, p
         rc, size, log = mosrx.bpf_jit_compile(ps)
@@ -323,7 +333,7 @@ def test_bpf_random_programs(gpu_ctx, engine, seed):
     z, _ = load()
     t = mosrx.Trace(mosrx.TRACE_IMIX, 4096, nflows=500, seed=seed)
     for buf, off, ln in ((z["frames"], z["off"], z["len"]), (t.frames[:t.frames_bytes], t.off, t.len)):
-        for ps in random_sets(seed):
+        for ps in random_sets(seed) + ret_a_sets(seed):
             bpf_set(gpu_ctx, engine, ps)
             np.testing.assert_array_equal(gpu_ctx.bpf_host(buf, off, ln), O.bpf_eval(ps, buf, off, ln))
 
