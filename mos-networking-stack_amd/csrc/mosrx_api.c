@@ -1264,164 +1264,6 @@ static int group_steer(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint3
 	return 0;
 }
 
-/* The device addresses of an armed group's forwarding outputs (mosrx_slot_fwd),
- * when every one of them is pinned and aligned to its stores: into the slot's
- * two forwarding tables. */
-static int fwd_outputs(int device, const mosrx_batch *b, uint32_t nb, const mosrx_slot_fwd_out *o, mosrx_fdesc *fd,
-                       mosrx_ddesc *dd)
-{
-	uint32_t i;
-	for (i = 0; i < nb; i++) {
-		const uint64_t n = b[i].n;
-		if (((uintptr_t)o->h_rings[i] & 15) ||
-		    !(dd[i].rings = mosrx__host_dev_of(o->h_rings[i], (uint64_t)o->nrings * sizeof(mosrx_fwd_ring), device)))
-			return 0;
-		fd[i].rings = dd[i].rings;
-		if (!n)
-			continue;
-		fd[i].plan = NULL;   /* (no h_plan: the slot's own array) */
-		if (o->h_plan && (((uintptr_t)o->h_plan[i] & 7) ||
-		                  !(fd[i].plan = mosrx__host_dev_of(o->h_plan[i], n * sizeof(mosrx_fwd), device))))
-			return 0;
-		if (!(dd[i].tx_src = mosrx__host_dev_of(o->h_tx_src[i], n * 4, device)) ||
-		    !(dd[i].tx_len = mosrx__host_dev_of(o->h_tx_len[i], n * 2, device)) ||
-		    !(dd[i].tx_mac = mosrx__host_dev_of(o->h_tx_mac[i], n * 12, device)))
-			return 0;
-	}
-	return 1;
-}
-
-static void fwd_mark_used(mosrx_ctx *c);
-
-/* The plan and descriptor launches over a queue's or a group's two tables,
- * whose largest batch has maxn frames: the one launch when the context's limit
- * admits every batch (mosrx_set_fwd_one), else -- and always with the limit at
- * 0 -- the four. */
-static int fwd_desc_queue_launch(mosrx_ctx *c, const mosrx_fqparams *fq, const mosrx_dqparams *dq, uint32_t maxn,
-                                 void *stream)
-{
-	mosrx_oparams op;
-	int rc;
-	if (!c->fwd_one || maxn > c->fwd_one)
-		return mosrx_launch_fwd_desc_queue(fq, dq, stream);
-	memset(&op, 0, sizeof(op));
-	op.fdesc = fq->desc;
-	op.ddesc = dq->desc;
-	op.tab = fq->tab;
-	op.nb = fq->nb;
-	op.rec_bytes = fq->rec_bytes;
-	op.forward = fq->forward;
-	op.num_msp = fq->num_msp;
-	op.listener = fq->listener;
-	op.nrings = fq->nrings;
-	if (!(rc = mosrx_launch_fwd_one(&op, stream)))
-		c->fwd_one_count++;
-	return rc;
-}
-
-/* The plan and descriptor launches of an armed group, behind its classify (and
- * steer) launches on the slot's stream: over the records and descriptors where
- * the classify launch wrote and read them (s->h_qdesc), into the caller's
- * pinned arrays (in_place: fwd_outputs filled the tables) or the slot's
- * buffers, which are then copied back per batch -- all n entries of each array:
- * those at and past the sent count then hold nothing of meaning. */
-static int group_fwd(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
-                     const mosrx_slot_fwd_out *o)
-{
-	mosrx_fqparams fq;
-	mosrx_dqparams dq;
-	uint32_t i, tiles = 0, maxn = 0;
-	uint64_t pre = 0;
-	int rc;
-	for (i = 0; i < nb; pre += b[i].n, i++) {
-		mosrx_fdesc *f = &s->h_fdesc[i];
-		mosrx_ddesc *d = &s->h_ddesc[i];
-		const mosrx_qdesc *q = &s->h_qdesc[i];
-		if (!in_place) {
-			f->plan = NULL;
-			d->rings = s->d_frings + (size_t)i * MOSRX_FWD_MAX_NETDEVS;
-			d->tx_src = b[i].n ? s->d_ftsrc + pre : NULL;
-			d->tx_len = b[i].n ? s->d_ftlen + pre : NULL;
-			d->tx_mac = b[i].n ? s->d_ftmac + 3 * pre : NULL;
-		}
-		if (!f->plan || !b[i].n)
-			f->plan = b[i].n ? s->d_fplan + pre : NULL;
-		f->rings = d->rings;
-		f->tx = NULL;
-		f->tx_off = NULL;
-		f->tx_len = NULL;
-		f->tx_src = NULL;
-		f->frames = d->frames = q->frames;
-		f->off = d->off = q->off;
-		f->len = q->len;
-		f->rec = (const uint8_t *)q->out;
-		d->plan = f->plan;
-		f->frames_bytes = d->frames_bytes = q->frames_bytes;
-		f->n = d->n = b[i].n;
-		f->in_ifidx = o->in_ifidx ? o->in_ifidx[i] : 0;
-		f->tile_base = d->tile_base = tiles;
-		d->pad = 0;
-		tiles += (b[i].n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
-		if (b[i].n > maxn)
-			maxn = b[i].n;
-	}
-	HIPCHK(hipMemcpyAsync(s->d_fdesc, s->h_fdesc, nb * sizeof(mosrx_fdesc), hipMemcpyHostToDevice, s->stream));
-	HIPCHK(hipMemcpyAsync(s->d_ddesc, s->h_ddesc, nb * sizeof(mosrx_ddesc), hipMemcpyHostToDevice, s->stream));
-	memset(&fq, 0, sizeof(fq));
-	memset(&dq, 0, sizeof(dq));
-	fq.desc = s->d_fdesc;
-	fq.tab = dq.tab = c->d_fwd;
-	fq.scratch = dq.scratch = s->d_fscr;
-	fq.nb = dq.nb = nb;
-	fq.total_tiles = dq.total_tiles = tiles;
-	fq.rec_bytes = (uint32_t)rsz;
-	fq.forward = c->params.forward;
-	fq.num_msp = c->params.num_msp;
-	fq.listener = c->fwd_listener;
-	fq.nrings = dq.nrings = o->nrings;
-	dq.desc = s->d_ddesc;
-	fwd_mark_used(c);
-	if ((rc = fwd_desc_queue_launch(c, &fq, &dq, maxn, (void *)s->stream)))
-		return rc;
-	for (i = 0, pre = 0; i < nb; pre += b[i].n, i++) {
-		const size_t n = b[i].n;
-		if (o->h_plan && n && s->h_fdesc[i].plan == s->d_fplan + pre)
-			HIPCHK(hipMemcpyAsync(o->h_plan[i], s->d_fplan + pre, n * sizeof(mosrx_fwd), hipMemcpyDeviceToHost, s->stream));
-		if (in_place)
-			continue;
-		HIPCHK(hipMemcpyAsync(o->h_rings[i], s->d_frings + (size_t)i * MOSRX_FWD_MAX_NETDEVS,
-		                      (size_t)o->nrings * sizeof(mosrx_fwd_ring), hipMemcpyDeviceToHost, s->stream));
-		if (!n)
-			continue;
-		HIPCHK(hipMemcpyAsync(o->h_tx_src[i], s->d_ftsrc + pre, n * 4, hipMemcpyDeviceToHost, s->stream));
-		HIPCHK(hipMemcpyAsync(o->h_tx_len[i], s->d_ftlen + pre, n * 2, hipMemcpyDeviceToHost, s->stream));
-		HIPCHK(hipMemcpyAsync(o->h_tx_mac[i], s->d_ftmac + 3 * pre, n * 12, hipMemcpyDeviceToHost, s->stream));
-	}
-	return 0;
-}
-
-int mosrx_slot_fwd(mosrx_ctx *c, int slot, const mosrx_slot_fwd_out *o)
-{
-	if (!c || slot < 0 || slot >= NSLOT)
-		return -EINVAL;
-	if (c->slot[slot].busy)
-		return -EBUSY;
-	if (!o) {
-		c->slot[slot].fwd_armed = 0;
-		return 0;
-	}
-	if (!o->h_tx_src || !o->h_tx_len || !o->h_tx_mac || !o->h_rings || o->nrings < 1 ||
-	    o->nrings > MOSRX_FWD_MAX_NETDEVS)
-		return -EINVAL;
-	if (!c->d_fwd)
-		return -ENOENT;
-	if (o->nrings < c->fwd_num_netdevs)
-		return -EINVAL;
-	c->slot[slot].fwd = *o;
-	c->slot[slot].fwd_armed = 1;
-	return 0;
-}
-
 int mosrx_classify_host_group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t nb,
                                      mosrx_result *const *h_out, mosrx_tcpinfo *const *h_tcpinfo)
 {
@@ -1473,20 +1315,13 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	fwd = s->fwd_armed;
 	fo = s->fwd;
 	s->fwd_armed = 0;
-	if (fwd && !c->d_fwd)
-		return -ENOENT;
-	if (fwd && fo.nrings < c->fwd_num_netdevs)
-		return -EINVAL;
+	if (fwd && (rc = mosrx__fwd_group_check(c, &fo)))
+		return rc;
 	for (i = 0; i < nb; i++) {
 		if ((rc = mosrx__check_batch(&b[i], 0)))
 			return rc;
-		if (fwd && (!fo.h_rings[i] || ((uintptr_t)fo.h_rings[i] & 3) ||
-		            (fo.in_ifidx && fo.in_ifidx[i] >= MOSRX_FWD_MAX_NETDEVS) ||
-		            (b[i].n && (!fo.h_tx_src[i] || !fo.h_tx_len[i] || !fo.h_tx_mac[i] ||
-		                        (((uintptr_t)fo.h_tx_src[i] | (uintptr_t)fo.h_tx_mac[i]) & 3) ||
-		                        ((uintptr_t)fo.h_tx_len[i] & 1) ||
-		                        (fo.h_plan && (!fo.h_plan[i] || ((uintptr_t)fo.h_plan[i] & 7)))))))
-			return -EINVAL;
+		if (fwd && (rc = mosrx__fwd_group_check_batch(&fo, i, b[i].n)))
+			return rc;
 		if (b[i].n && (!h_out[i] || (h_tcpinfo && !h_tcpinfo[i]) || (h_fhash && !h_fhash[i]) ||
 		               (h_match && !h_match[i]) ||
 		               (h_sidx && (!h_sidx[i] || !h_sqs[i] || (((uintptr_t)h_sidx[i] | (uintptr_t)h_sqs[i]) & 3))) ||
@@ -1511,8 +1346,8 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 		                          mosrx__host_range_of(b[i].len, (uint64_t)b[i].n * 2)};
 	}
 	if (ntot == 0) {
-		for (i = 0; fwd && i < nb; i++)   /* n == 0: the zeroed rings only */
-			memset(fo.h_rings[i], 0, (size_t)fo.nrings * sizeof(mosrx_fwd_ring));
+		if (fwd)   /* n == 0: the zeroed rings only */
+			mosrx__fwd_group_empty(&fo, nb);
 		s->busy = 2;
 		s->direct = 0;
 		return 0;
@@ -1523,7 +1358,7 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	             (!h_sidx || steer_outputs(c->device, b, nb, h_sidx, h_sqs, s->h_sdesc)) &&
 	             (!go.qrec || gather_outputs(c->device, b, nb, rsz, &go, s->h_gdesc)) &&
 	             (!GATHER_SIDE(&go) || side_outputs(c->device, b, nb, &go, s->h_xdesc)) &&
-	             (!fwd || fwd_outputs(c->device, b, nb, &fo, s->h_fdesc, s->h_ddesc));
+	             (!fwd || mosrx__fwd_group_outputs(c->device, b, nb, &fo, s->h_fdesc, s->h_ddesc));
 	if (!direct) {
 		group_copy(s, r, nr, &dev_bytes, 0);
 		if ((rc = mosrx__slot_reserve(c, s, dev_bytes, ntot)))
@@ -1616,7 +1451,7 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	s->timed = c->timing;
 	if (h_sidx && (rc = group_steer(c, s, b, nb, rsz, out_direct, h_sidx, h_sqs, &go)))
 		return rc;
-	if (fwd && (rc = group_fwd(c, s, b, nb, rsz, out_direct, &fo)))
+	if (fwd && (rc = mosrx__fwd_group_launch(c, s, b, nb, rsz, out_direct, &fo)))
 		return rc;
 	/* results: one copy when the host buffers follow each other, else per batch */
 	for (i = 0, pre = 0; !out_direct && i < nb;) {
@@ -2042,51 +1877,7 @@ static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
 	return 0;
 }
 
-/* MOSRX_OP_FWD's / MOSRX_OP_FWD_RINGS' TX outputs + scratch: one block for the
- * context stream and one per timing stream, sized for the largest batch (each
- * part rounded to 256 bytes): tx_frames as `nrings` rings (MOSRX_OP_FWD: one),
- * each with room for every frame of the batch sent whole (its frame bytes + 32
- * a frame; the rings together at most 4 GiB), tx_off, tx_src, tx_len, tx_nif,
- * tx_count / the ring rows, scratch.  MOSRX_OP_FWD_DESC takes the same block:
- * its tx_mac (12 bytes an entry) lies where the rings would (each has room for
- * 32 bytes a frame). */
 #define OP_IS_FWD(op) ((op) == MOSRX_OP_FWD_PLAN || (op) == MOSRX_OP_FWD || (op) == MOSRX_OP_FWD_RINGS || (op) == MOSRX_OP_FWD_DESC)
-static int fwd_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, uint32_t nrings)
-{
-	uint32_t i, maxn = 0;
-	uint64_t maxb = 0, cap;
-	size_t stride, bytes;
-	for (i = 0; i < nb; i++) {
-		maxn = b[i].n > maxn ? b[i].n : maxn;
-		maxb = b[i].frames_bytes > maxb ? b[i].frames_bytes : maxb;
-	}
-	cap = STEER_TMP_RND(maxb + 32ull * maxn);
-	if (nrings > 1 && cap > ((1ull << 32) / nrings & ~255ull))
-		cap = (1ull << 32) / nrings & ~255ull;
-	c->fwd_tmp_n = maxn;
-	c->fwd_tmp_cap = cap;
-	c->fwd_tmp_rings = nrings;
-	stride = c->fwd_tmp_cap * nrings + 2 * STEER_TMP_RND((size_t)maxn * 4) + STEER_TMP_RND((size_t)maxn * 2) +
-	         STEER_TMP_RND(maxn) + 256 + STEER_TMP_RND(mosrx_fwd_rings_scratch_bytes(maxn, nrings));
-	bytes = stride * (MOSRX_MAX_STREAMS + 1);
-	if (bytes > c->fwd_tmp_bytes) {
-		HIPCHK(hipDeviceSynchronize());
-		if (c->fwd_tmp)
-			hipFree(c->fwd_tmp);
-		c->fwd_tmp = NULL;
-		c->fwd_tmp_bytes = 0;
-		if (hipMalloc((void **)&c->fwd_tmp, bytes) != hipSuccess)
-			return -ENOMEM;
-		c->fwd_tmp_bytes = bytes;
-	}
-	c->fwd_tmp_stride = stride;
-	return 0;
-}
-
-static int fwd_plan_desc_one(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, int in_ifidx,
-                             mosrx_fwd *d_plan, uint32_t nrings, uint32_t *d_tx_src, uint16_t *d_tx_len,
-                             uint32_t *d_tx_mac, mosrx_fwd_ring *d_rings, void *d_scratch, size_t scratch_bytes,
-                             hipStream_t s);
 
 /* One enqueue of operation `op` on batch b (see mosrx_time_op). */
 static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out, void *aux, hipStream_t s)
@@ -2143,41 +1934,7 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 	case MOSRX_OP_FWD_PLAN:
 	case MOSRX_OP_FWD:
 	case MOSRX_OP_FWD_RINGS:
-	case MOSRX_OP_FWD_DESC: {
-		uint32_t k = 0;
-		uint8_t *blk, *toff, *tsrc, *tlen, *tnif, *tcnt, *scr;
-		const size_t w = STEER_TMP_RND((size_t)c->fwd_tmp_n * 4);
-		/* the descriptor form under mosrx_set_fwd_one's limit: plan and rings in one launch, below */
-		const int one = op == MOSRX_OP_FWD_DESC && c->fwd_one && b->n <= c->fwd_one;
-		int rc = one ? 0 : mosrx_fwd_plan_dev(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, s);
-		if (rc || op == MOSRX_OP_FWD_PLAN)
-			return rc;
-		while (k < c->nxs && c->xs[k] != s)
-			k++;
-		blk = c->fwd_tmp + (size_t)(k < c->nxs ? k + 1 : 0) * c->fwd_tmp_stride;
-		toff = blk + c->fwd_tmp_cap * c->fwd_tmp_rings;
-		tsrc = toff + w;
-		tlen = tsrc + w;
-		tnif = tlen + STEER_TMP_RND((size_t)c->fwd_tmp_n * 2);
-		tcnt = tnif + STEER_TMP_RND(c->fwd_tmp_n);
-		scr = tcnt + 256;
-		if (one)
-			return fwd_plan_desc_one(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, c->fwd_tmp_rings, (uint32_t *)tsrc,
-			                         (uint16_t *)tlen, (uint32_t *)blk, (mosrx_fwd_ring *)tcnt, scr,
-			                         STEER_TMP_RND(mosrx_fwd_desc_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)), s);
-		if (op == MOSRX_OP_FWD_DESC)
-			return mosrx_fwd_desc_rings_dev(c, b, (const mosrx_fwd *)aux, c->fwd_tmp_rings, (uint32_t *)tsrc, (uint16_t *)tlen,
-			                                (uint32_t *)blk, (mosrx_fwd_ring *)tcnt, scr,
-			                                STEER_TMP_RND(mosrx_fwd_desc_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)), s);
-		if (op == MOSRX_OP_FWD_RINGS)
-			return mosrx_fwd_build_rings_dev(c, b, (const mosrx_fwd *)aux, blk, c->fwd_tmp_cap, c->fwd_tmp_rings,
-			                                 (uint32_t *)toff, (uint16_t *)tlen, (uint32_t *)tsrc, (mosrx_fwd_ring *)tcnt,
-			                                 scr, STEER_TMP_RND(mosrx_fwd_rings_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)),
-			                                 s);
-		return mosrx_fwd_build_dev(c, b, (const mosrx_fwd *)aux, blk, c->fwd_tmp_cap, (uint32_t *)toff, (uint16_t *)tlen,
-		                           (int8_t *)tnif, (uint32_t *)tsrc, (uint32_t *)tcnt, scr,
-		                           STEER_TMP_RND(mosrx_fwd_scratch_bytes(c->fwd_tmp_n)), s);
-	}
+	case MOSRX_OP_FWD_DESC: return mosrx__fwd_op(c, op, arg, b, out, aux, s);
 	default: return -EINVAL;
 	}
 }
@@ -2275,14 +2032,8 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 	HIPCHK(hipSetDevice(c->device));
 	if (OP_IS_STEER(op) && (rc = steer_tmp_reserve(c, b, nb)))
 		return rc;
-	if (op == MOSRX_OP_FWD && (rc = fwd_tmp_reserve(c, b, nb, 1)))
+	if (OP_IS_FWD(op) && (rc = mosrx__fwd_tmp_reserve(c, op, b, nb)))
 		return rc;
-	if (op == MOSRX_OP_FWD_RINGS || op == MOSRX_OP_FWD_DESC) {
-		if (!c->d_fwd)
-			return -ENOENT;
-		if ((rc = fwd_tmp_reserve(c, b, nb, c->fwd_num_netdevs ? c->fwd_num_netdevs : 1)))
-			return rc;
-	}
 	if (total_ms && (rc = time_streams(c, op, arg, b, nb, out, aux, iters, nstreams, total_ms)))
 		return rc;
 	if (avg_kernel_ms && (rc = time_kernels(c, op, arg, b, nb, out, aux, iters, avg_kernel_ms)))
@@ -2462,47 +2213,6 @@ int mosrx_device_sync(mosrx_ctx *c)
 }
 
 /* ---- batch queue (one launch over many resident batches) ---- */
-struct mosrx_queue {
-	mosrx_qdesc *d_desc;
-	mosrx_qdesc *h_desc;   /* host copy: the per-batch BPF launches of a queue with masks */
-	uint32_t nb;
-	uint32_t total_tiles;
-	uint32_t tpb;   /* tiles per batch if uniform, else 0 */
-	int tile;
-	uint64_t bytes, n;   /* frame bytes and frames of all batches (tail policy) */
-	int compact;         /* 8-byte records */
-	int uni;             /* some batch carries a layout hint */
-	int match;           /* the descriptors' bmatch: the installed BPF set's masks */
-	uint32_t **d_match;  /* per batch (the non-fused form) */
-	/* queue steering (mosrx_queue_set_steer): the batches' steer table and the
-	 * histogram rows, allocated at the first attach; steer: outputs attached */
-	mosrx_sdesc *d_sdesc;
-	uint32_t *d_shist;
-	uint32_t steer_tiles;
-	uint32_t steer_maxn;   /* the largest batch, kept at attach: a run takes the one-launch form by it */
-	int steer;
-	/* its gather form (mosrx_queue_set_steer_gather): the table parallel to
-	 * d_sdesc; gather: the scatter pass of a run is the gather form */
-	mosrx_gdesc *d_gdesc;
-	int gather;
-	/* ... and its side form (mosrx_queue_set_steer_gather_side), the third table */
-	mosrx_xdesc *d_xdesc;
-	int side;
-	/* forwarding (mosrx_queue_set_fwd): the batches' table and the build's
-	 * scratch rows, allocated at the first attach that needs them; fwd: a plan
-	 * attached, fwd_build: with the ring build */
-	mosrx_fdesc *d_fdesc;
-	uint32_t *d_fscratch;
-	size_t fscratch_rows;
-	uint32_t fwd_tiles, fwd_nrings, fwd_cap_units;
-	int fwd, fwd_build;
-	/* its descriptor form (mosrx_queue_set_fwd_desc): the store launch's table,
-	 * parallel to d_fdesc; fwd_desc: attached (then fwd is set, fwd_build is not) */
-	mosrx_ddesc *d_ddesc;
-	int fwd_desc;
-	uint32_t fwd_maxn;   /*   its largest batch: what mosrx_set_fwd_one's limit is held against */
-};
-
 int mosrx_queue_create_ex(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb, void *const *d_out,
                           uint32_t *const *d_fhash, uint32_t *const *d_match, int flags, mosrx_queue **q)
 {
@@ -2620,9 +2330,6 @@ static int queue_classify(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 	return 0;
 }
 
-static int queue_fwd_check(const mosrx_ctx *c, const mosrx_queue *q);
-static int queue_fwd(mosrx_ctx *c, const mosrx_queue *q, void *stream);
-
 static int queue_steer(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 {
 	mosrx_sparams sp;
@@ -2647,13 +2354,13 @@ int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 {
 	int rc;
 	/* forwarding's run-time conditions first: a run that cannot forward enqueues nothing */
-	if (c && q && q->fwd && (rc = queue_fwd_check(c, q)))
+	if (c && q && q->fwd && (rc = mosrx__fwd_queue_check(c, q)))
 		return rc;
 	if ((rc = queue_classify(c, q, stream)))
 		return rc;
 	if (q->steer && (rc = queue_steer(c, q, stream)))
 		return rc;
-	return q->fwd ? queue_fwd(c, q, stream) : 0;
+	return q->fwd ? mosrx__fwd_queue_launch(c, q, stream) : 0;
 }
 
 static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
@@ -2840,18 +2547,6 @@ uint32_t mosrx_get_steer_one(const mosrx_ctx *c) { return c ? c->steer_one : 0; 
 
 uint64_t mosrx_steer_one_count(const mosrx_ctx *c) { return c ? c->steer_one_count : 0; }
 
-int mosrx_set_fwd_one(mosrx_ctx *c, uint32_t max_frames)
-{
-	if (!c || max_frames > MOSRX_FWD_ONE_MAX)
-		return -EINVAL;
-	c->fwd_one = max_frames;
-	return 0;
-}
-
-uint32_t mosrx_get_fwd_one(const mosrx_ctx *c) { return c ? c->fwd_one : 0; }
-
-uint64_t mosrx_fwd_one_count(const mosrx_ctx *c) { return c ? c->fwd_one_count : 0; }
-
 int mosrx_steer_dev(mosrx_ctx *c, const void *d_rec, uint32_t n, int rec_bytes, uint32_t *d_idx, uint32_t *d_qstart,
                     void *d_scratch, size_t scratch_bytes, void *stream)
 {
@@ -2978,609 +2673,5 @@ int mosrx_time_queue(mosrx_ctx *c, mosrx_queue *const *q, uint32_t nq, uint32_t 
 		}
 		*avg_kernel_ms = (float)(tot / (i ? i : 1));
 	}
-	return 0;
-}
-
-/* ---- forwarding (csrc/mosrx_fwd.hip) ---------------------------------------- */
-
-size_t mosrx_fwd_scratch_bytes(uint32_t n)
-{
-	const size_t tiles = ((size_t)n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
-	return (tiles ? tiles : 1) * MOSRX_FWD_ROW;
-}
-
-uint32_t mosrx_fwd_tile(void) { return MOSRX_FWD_TILE; }
-
-/* one row per tile and ring; nrings outside 1 .. MOSRX_FWD_MAX_NETDEVS is
- * clamped, so the size is defined (and monotone) for every argument */
-size_t mosrx_fwd_rings_scratch_bytes(uint32_t n, uint32_t nrings)
-{
-	const size_t tiles = ((size_t)n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
-	const size_t q = nrings < 1 ? 1 : nrings > MOSRX_FWD_MAX_NETDEVS ? MOSRX_FWD_MAX_NETDEVS : nrings;
-	return (tiles ? tiles : 1) * q * MOSRX_FWD_ROW;
-}
-
-int mosrx_fwd_set_listener(mosrx_ctx *c, int listener)
-{
-	if (!c)
-		return -EINVAL;
-	c->fwd_listener = listener != 0;
-	return 0;
-}
-
-/* The tables go to the next buffer of a pool, as the BPF instruction buffers
- * do (bpf_api.c stage_insns): launches submitted earlier may still read the
- * copy they were given, so a buffer is written again only after those launches
- * drained, and only if a launch may have read it since its last write. */
-int mosrx_fwd_set(mosrx_ctx *c, const mosrx_fwd_tables *t)
-{
-	mosrx_fwd_dev *h;
-	uint32_t i, k;
-	int rc;
-	if (!c)
-		return -EINVAL;
-	if (!t) {
-		c->d_fwd = NULL;
-		c->fwd_num_netdevs = 0;
-		return 0;
-	}
-	if (t->num_routes > MOSRX_FWD_MAX_ROUTES || t->num_arp > MOSRX_FWD_MAX_ARP ||
-	    t->num_netdevs > MOSRX_FWD_MAX_NETDEVS)
-		return -EINVAL;
-	for (i = 0; i < t->num_routes; i++)
-		if (t->routes[i].nif < 0 || (uint32_t)t->routes[i].nif >= t->num_netdevs)
-			return -EINVAL;
-	for (i = 0; t->has_nic_fwd && i < MOSRX_FWD_MAX_NETDEVS; i++)
-		if (t->nic_fwd[i] != -1 && (t->nic_fwd[i] < 0 || (uint32_t)t->nic_fwd[i] >= t->num_netdevs))
-			return -EINVAL;
-	if (!(h = calloc(1, sizeof(*h))))
-		return -ENOMEM;
-	h->num_routes = t->num_routes;
-	h->num_arp = t->num_arp;
-	h->num_netdevs = t->num_netdevs;
-	h->has_nic_fwd = t->has_nic_fwd != 0;
-	memcpy(h->nic_fwd, t->nic_fwd, sizeof(h->nic_fwd));
-	for (i = 0; i < MOSRX_FWD_MAX_NETDEVS; i++)
-		memcpy(h->netdev_haddr[i], t->netdev_haddr[i], 6);
-	for (i = 0; i < t->num_routes; i++) {
-		h->r_mask[i] = t->routes[i].mask;
-		h->r_masked[i] = t->routes[i].masked_ip;
-		h->r_prefix[i] = t->routes[i].prefix;
-		h->r_nif[i] = t->routes[i].nif;
-	}
-	for (i = 0; i < t->num_arp; i++) {
-		/* prefix 1 is GetDestinationHWaddr's exact-address form (arp.c:102-106) */
-		const int exact = t->arp[i].prefix == 1;
-		h->a_mask[i] = exact ? 0xFFFFFFFFu : t->arp[i].mask;
-		h->a_masked[i] = exact ? t->arp[i].ip : t->arp[i].masked_ip;
-		h->a_prefix[i] = t->arp[i].prefix;
-		memcpy(h->a_haddr[i], t->arp[i].haddr, 6);
-	}
-	rc = 0;
-	k = c->fwd_pool_next;
-	if (hipSetDevice(c->device) != hipSuccess)
-		rc = -EIO;
-	if (!rc && !c->d_fwd_pool[k] && hipMalloc((void **)&c->d_fwd_pool[k], sizeof(*h)) != hipSuccess)
-		rc = -ENOMEM;
-	if (!rc && c->fwd_pool_used[k] && !(rc = mosrx__drain(c)))
-		memset(c->fwd_pool_used, 0, sizeof(c->fwd_pool_used));
-	if (!rc && hipMemcpy(c->d_fwd_pool[k], h, sizeof(*h), hipMemcpyHostToDevice) != hipSuccess)
-		rc = -EIO;
-	free(h);
-	if (rc)
-		return rc;
-	c->d_fwd = c->d_fwd_pool[k];
-	c->fwd_num_netdevs = t->num_netdevs;
-	c->fwd_pool_next = (k + 1) % MOSRX_FWD_POOL;
-	return 0;
-}
-
-/* A launch that reads the installed tables is about to go to stream. */
-static void fwd_mark_used(mosrx_ctx *c)
-{
-	c->fwd_pool_used[(c->fwd_pool_next + MOSRX_FWD_POOL - 1) % MOSRX_FWD_POOL] = 1;
-}
-
-static int fwd_batch(const mosrx_ctx *c, const mosrx_batch *b, mosrx_fparams *fp)
-{
-	int rc;
-	if ((rc = mosrx__check_batch(b, 1)))
-		return rc;
-	if (b->n && ((((uintptr_t)b->off) & 3) || (((uintptr_t)b->len) & 1)))
-		return -EINVAL;
-	memset(fp, 0, sizeof(*fp));
-	fp->frames = b->frames;
-	fp->off = b->off;
-	fp->len = b->len;
-	fp->frames_bytes = (uint32_t)b->frames_bytes;
-	fp->n = b->n;
-	fp->tab = c->d_fwd;
-	return 0;
-}
-
-int mosrx_fwd_plan_dev(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, int in_ifidx,
-                       mosrx_fwd *d_plan, void *stream)
-{
-	mosrx_fparams fp;
-	hipStream_t s;
-	int rc;
-	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || (rec_bytes != 8 && rec_bytes != 16) || in_ifidx < 0 ||
-	    in_ifidx >= MOSRX_FWD_MAX_NETDEVS || (b->n && (!d_rec || ((uintptr_t)d_rec & (uintptr_t)(rec_bytes - 1)))))
-		return -EINVAL;
-	if ((rc = fwd_batch(c, b, &fp)))
-		return rc;
-	if (!c->d_fwd)
-		return -ENOENT;
-	if (b->n == 0)
-		return 0;
-	fp.rec = (const uint8_t *)d_rec;
-	fp.rec_bytes = (uint32_t)rec_bytes;
-	fp.in_ifidx = in_ifidx;
-	fp.plan = d_plan;
-	fp.forward = c->params.forward;
-	fp.num_msp = c->params.num_msp;
-	fp.listener = c->fwd_listener;
-	s = stream ? (hipStream_t)stream : c->stream;
-	HIPCHK(hipSetDevice(c->device));
-	fwd_mark_used(c);
-	rc = mosrx_launch_fwd_plan(&fp, (void *)s);
-	mosrx__note_stream(c, s);   /* (after the launch: its event covers it) */
-	return rc;
-}
-
-int mosrx_fwd_build_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint8_t *d_tx_frames,
-                        uint64_t tx_cap, uint32_t *d_tx_off, uint16_t *d_tx_len, int8_t *d_tx_nif,
-                        uint32_t *d_tx_src, uint32_t *d_tx_count, void *d_scratch, size_t scratch_bytes, void *stream)
-{
-	mosrx_fparams fp;
-	hipStream_t s;
-	int rc;
-	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || !d_tx_frames || ((uintptr_t)d_tx_frames & 15) || !d_tx_off ||
-	    ((uintptr_t)d_tx_off & 3) || !d_tx_len || ((uintptr_t)d_tx_len & 1) || !d_tx_nif || !d_tx_src ||
-	    ((uintptr_t)d_tx_src & 3) || !d_tx_count || ((uintptr_t)d_tx_count & 3) || !d_scratch ||
-	    ((uintptr_t)d_scratch & 15) || scratch_bytes < mosrx_fwd_scratch_bytes(b->n))
-		return -EINVAL;
-	if ((rc = fwd_batch(c, b, &fp)))
-		return rc;
-	if (!c->d_fwd)
-		return -ENOENT;
-	fp.plan = (mosrx_fwd *)d_plan;
-	/* tx_off is a u32: room past 4 GiB is never used */
-	fp.cap_units = (uint32_t)((tx_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : tx_cap) / 16);
-	fp.tx = d_tx_frames;
-	fp.tx_off = d_tx_off;
-	fp.tx_len = d_tx_len;
-	fp.tx_nif = d_tx_nif;
-	fp.tx_src = d_tx_src;
-	fp.tx_count = d_tx_count;
-	fp.scratch = (uint32_t *)d_scratch;
-	fp.tiles = (b->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
-	s = stream ? (hipStream_t)stream : c->stream;
-	HIPCHK(hipSetDevice(c->device));
-	fwd_mark_used(c);
-	rc = mosrx_launch_fwd_build(&fp, (void *)s);
-	mosrx__note_stream(c, s);
-	return rc;
-}
-
-int mosrx_fwd_build_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint8_t *d_tx_frames,
-                              uint64_t ring_cap, uint32_t nrings, uint32_t *d_tx_off, uint16_t *d_tx_len,
-                              uint32_t *d_tx_src, mosrx_fwd_ring *d_rings, void *d_scratch, size_t scratch_bytes,
-                              void *stream)
-{
-	mosrx_fparams fp;
-	mosrx_rparams rp;
-	hipStream_t s;
-	int rc;
-	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || !d_tx_frames || ((uintptr_t)d_tx_frames & 15) || !d_tx_off ||
-	    ((uintptr_t)d_tx_off & 3) || !d_tx_len || ((uintptr_t)d_tx_len & 1) || !d_tx_src || ((uintptr_t)d_tx_src & 3) ||
-	    !d_rings || ((uintptr_t)d_rings & 15) || !d_scratch || ((uintptr_t)d_scratch & 15) || nrings < 1 ||
-	    nrings > MOSRX_FWD_MAX_NETDEVS || (ring_cap & 15) || ring_cap > (1ull << 32) ||
-	    ring_cap * nrings > (1ull << 32) /* tx_off is a u32 */ ||
-	    scratch_bytes < mosrx_fwd_rings_scratch_bytes(b->n, nrings))
-		return -EINVAL;
-	if ((rc = fwd_batch(c, b, &fp)))
-		return rc;
-	if (!c->d_fwd)
-		return -ENOENT;
-	if (nrings < c->fwd_num_netdevs)
-		return -EINVAL;
-	memset(&rp, 0, sizeof(rp));
-	rp.frames = fp.frames;
-	rp.off = fp.off;
-	rp.tab = fp.tab;
-	rp.plan = d_plan;
-	rp.frames_bytes = fp.frames_bytes;
-	rp.n = fp.n;
-	rp.nrings = nrings;
-	rp.cap_units = (uint32_t)(ring_cap / 16);
-	rp.tiles = (b->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
-	rp.tx = d_tx_frames;
-	rp.tx_off = d_tx_off;
-	rp.tx_len = d_tx_len;
-	rp.tx_src = d_tx_src;
-	rp.rings = d_rings;
-	rp.scratch = (uint32_t *)d_scratch;
-	s = stream ? (hipStream_t)stream : c->stream;
-	HIPCHK(hipSetDevice(c->device));
-	fwd_mark_used(c);
-	rc = mosrx_launch_fwd_rings(&rp, (void *)s);
-	mosrx__note_stream(c, s);
-	return rc;
-}
-
-/* ---- forwarding over a batch queue (mosrx_queue_set_fwd) ---- */
-
-static int queue_fwd_check(const mosrx_ctx *c, const mosrx_queue *q)
-{
-	if (!c->d_fwd)
-		return -ENOENT;
-	if ((q->fwd_build || q->fwd_desc) && q->fwd_nrings < c->fwd_num_netdevs)
-		return -EINVAL;
-	return 0;
-}
-
-/* The plan launch and, with TX outputs attached, the build's three, behind
- * whatever the run already put on the stream. */
-static int queue_fwd(mosrx_ctx *c, const mosrx_queue *q, void *stream)
-{
-	mosrx_fqparams fq;
-	const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-	int rc;
-	memset(&fq, 0, sizeof(fq));
-	fq.desc = q->d_fdesc;
-	fq.tab = c->d_fwd;
-	fq.scratch = q->d_fscratch;
-	fq.nb = q->nb;
-	fq.total_tiles = q->fwd_tiles;
-	fq.rec_bytes = q->compact ? 8u : 16u;
-	fq.forward = c->params.forward;
-	fq.num_msp = c->params.num_msp;
-	fq.listener = c->fwd_listener;
-	fq.nrings = q->fwd_nrings;
-	fq.cap_units = q->fwd_cap_units;
-	HIPCHK(hipSetDevice(c->device));
-	fwd_mark_used(c);
-	if (q->fwd_desc) {
-		mosrx_dqparams dq;
-		memset(&dq, 0, sizeof(dq));
-		dq.desc = q->d_ddesc;
-		dq.tab = fq.tab;
-		dq.scratch = fq.scratch;
-		dq.nb = fq.nb;
-		dq.total_tiles = fq.total_tiles;
-		dq.nrings = fq.nrings;
-		rc = fwd_desc_queue_launch(c, &fq, &dq, q->fwd_maxn, (void *)s);
-	} else
-		rc = mosrx_launch_fwd_queue(&fq, q->fwd_build, (void *)s);
-	mosrx__note_stream(c, s);   /* (after the launches: its event covers them) */
-	return rc;
-}
-
-int mosrx_queue_set_fwd(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd *f)
-{
-	mosrx_fdesc *h;
-	uint32_t i, tiles = 0;
-	size_t rows;
-	int build;
-	if (!c || !q)
-		return -EINVAL;
-	if (!f) {
-		if (!q->fwd_desc)   /* (the descriptor form is detached by its own call) */
-			q->fwd = q->fwd_build = 0;
-		return 0;
-	}
-	if (q->fwd_desc)
-		return -EINVAL;
-	build = f->d_tx_frames || f->d_tx_off || f->d_tx_len || f->d_tx_src || f->d_rings;
-	if (!f->d_plan || (build && (!f->d_tx_frames || !f->d_tx_off || !f->d_tx_len || !f->d_tx_src || !f->d_rings)))
-		return -EINVAL;
-	if (build && (f->nrings < 1 || f->nrings > MOSRX_FWD_MAX_NETDEVS || (f->ring_cap & 15) ||
-	              f->ring_cap > (1ull << 32) || f->ring_cap * f->nrings > (1ull << 32) /* tx_off is a u32 */))
-		return -EINVAL;
-	for (i = 0; i < q->nb; i++) {
-		if (f->in_ifidx && f->in_ifidx[i] >= MOSRX_FWD_MAX_NETDEVS)
-			return -EINVAL;
-		if (build && (!f->d_rings[i] || ((uintptr_t)f->d_rings[i] & 15)))
-			return -EINVAL;
-		if (!q->h_desc[i].n)
-			continue;
-		if (!f->d_plan[i] || ((uintptr_t)f->d_plan[i] & 7) || ((uintptr_t)q->h_desc[i].off & 3) ||
-		    ((uintptr_t)q->h_desc[i].len & 1))
-			return -EINVAL;
-		if (build && (!f->d_tx_frames[i] || ((uintptr_t)f->d_tx_frames[i] & 15) || !f->d_tx_off[i] ||
-		              ((uintptr_t)f->d_tx_off[i] & 3) || !f->d_tx_len[i] || ((uintptr_t)f->d_tx_len[i] & 1) ||
-		              !f->d_tx_src[i] || ((uintptr_t)f->d_tx_src[i] & 3)))
-			return -EINVAL;
-	}
-	if (!(h = calloc(q->nb, sizeof(*h))))
-		return -ENOMEM;
-	for (i = 0; i < q->nb; i++) {
-		const mosrx_qdesc *d = &q->h_desc[i];
-		h[i].n = d->n;
-		h[i].tile_base = tiles;
-		h[i].in_ifidx = f->in_ifidx ? f->in_ifidx[i] : 0;
-		h[i].rings = build ? f->d_rings[i] : NULL;
-		tiles += (d->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
-		if (!d->n)
-			continue;
-		h[i].frames = d->frames;
-		h[i].off = d->off;
-		h[i].len = d->len;
-		h[i].rec = (const uint8_t *)d->out;
-		h[i].frames_bytes = d->frames_bytes;
-		h[i].plan = f->d_plan[i];
-		if (build) {
-			h[i].tx = f->d_tx_frames[i];
-			h[i].tx_off = f->d_tx_off[i];
-			h[i].tx_len = f->d_tx_len[i];
-			h[i].tx_src = f->d_tx_src[i];
-		}
-	}
-	q->fwd = q->fwd_build = 0;
-	rows = build ? ((size_t)tiles ? tiles : 1) * f->nrings : 0;
-	if (hipSetDevice(c->device) != hipSuccess) {
-		free(h);
-		return -EIO;
-	}
-	if (rows > q->fscratch_rows) {
-		if (q->d_fscratch)
-			hipFree(q->d_fscratch);
-		q->d_fscratch = NULL;
-		q->fscratch_rows = 0;
-		if (hipMalloc((void **)&q->d_fscratch, rows * MOSRX_FWD_ROW) != hipSuccess) {
-			free(h);
-			return -ENOMEM;
-		}
-		q->fscratch_rows = rows;
-	}
-	if (!q->d_fdesc && hipMalloc((void **)&q->d_fdesc, (size_t)q->nb * sizeof(*h)) != hipSuccess) {
-		free(h);
-		return -ENOMEM;
-	}
-	if (hipMemcpy(q->d_fdesc, h, (size_t)q->nb * sizeof(*h), hipMemcpyHostToDevice) != hipSuccess) {
-		free(h);
-		return -EIO;
-	}
-	free(h);
-	q->fwd_tiles = tiles;
-	q->fwd_nrings = build ? f->nrings : 0;
-	q->fwd_cap_units = build ? (uint32_t)(f->ring_cap / 16) : 0;
-	q->fwd_build = build;
-	q->fwd = 1;
-	return 0;
-}
-
-/* ---- the descriptor form of the ring build ---- */
-
-size_t mosrx_fwd_desc_scratch_bytes(uint32_t n, uint32_t nrings)
-{
-	return mosrx_fwd_rings_scratch_bytes(n, nrings);
-}
-
-/* The one launch over the single batch in dp (n <= MOSRX_FWD_ONE_MAX); with fp,
- * the plan first, from its records, length array, in_ifidx and record size. */
-static int fwd_one_batch(mosrx_ctx *c, const mosrx_dparams *dp, const mosrx_fparams *fp, hipStream_t s)
-{
-	mosrx_oparams op;
-	int rc;
-	memset(&op, 0, sizeof(op));
-	op.tab = dp->tab;
-	op.nb = 1;
-	op.nrings = dp->nrings;
-	op.oned.frames = dp->frames;
-	op.oned.off = dp->off;
-	op.oned.plan = dp->plan;
-	op.oned.tx_src = dp->tx_src;
-	op.oned.tx_len = dp->tx_len;
-	op.oned.tx_mac = dp->tx_mac;
-	op.oned.rings = dp->rings;
-	op.oned.frames_bytes = dp->frames_bytes;
-	op.oned.n = dp->n;
-	if (fp) {
-		op.rec_bytes = fp->rec_bytes;
-		op.forward = c->params.forward;
-		op.num_msp = c->params.num_msp;
-		op.listener = c->fwd_listener;
-		op.onef.len = fp->len;
-		op.onef.rec = fp->rec;
-		op.onef.plan = (mosrx_fwd *)dp->plan;
-		op.onef.in_ifidx = (uint32_t)fp->in_ifidx;
-	}
-	if (!(rc = mosrx_launch_fwd_one(&op, (void *)s)))
-		c->fwd_one_count++;
-	return rc;
-}
-
-int mosrx_fwd_desc_rings_dev(mosrx_ctx *c, const mosrx_batch *b, const mosrx_fwd *d_plan, uint32_t nrings,
-                             uint32_t *d_tx_src, uint16_t *d_tx_len, uint32_t *d_tx_mac, mosrx_fwd_ring *d_rings,
-                             void *d_scratch, size_t scratch_bytes, void *stream)
-{
-	mosrx_fparams fp;
-	mosrx_dparams dp;
-	hipStream_t s;
-	int rc;
-	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || !d_tx_src || ((uintptr_t)d_tx_src & 3) || !d_tx_len ||
-	    ((uintptr_t)d_tx_len & 1) || !d_tx_mac || ((uintptr_t)d_tx_mac & 3) || !d_rings || ((uintptr_t)d_rings & 15) ||
-	    !d_scratch || ((uintptr_t)d_scratch & 15) || nrings < 1 || nrings > MOSRX_FWD_MAX_NETDEVS ||
-	    scratch_bytes < mosrx_fwd_desc_scratch_bytes(b->n, nrings))
-		return -EINVAL;
-	if ((rc = fwd_batch(c, b, &fp)))
-		return rc;
-	if (!c->d_fwd)
-		return -ENOENT;
-	if (nrings < c->fwd_num_netdevs)
-		return -EINVAL;
-	memset(&dp, 0, sizeof(dp));
-	dp.frames = fp.frames;
-	dp.off = fp.off;
-	dp.tab = fp.tab;
-	dp.plan = d_plan;
-	dp.frames_bytes = fp.frames_bytes;
-	dp.n = fp.n;
-	dp.nrings = nrings;
-	dp.tiles = (b->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
-	dp.tx_src = d_tx_src;
-	dp.tx_len = d_tx_len;
-	dp.tx_mac = d_tx_mac;
-	dp.rings = d_rings;
-	dp.scratch = (uint32_t *)d_scratch;
-	s = stream ? (hipStream_t)stream : c->stream;
-	HIPCHK(hipSetDevice(c->device));
-	fwd_mark_used(c);
-	if (c->fwd_one && b->n <= c->fwd_one)
-		rc = fwd_one_batch(c, &dp, NULL, s);   /* (the scratch is left as it is) */
-	else
-		rc = mosrx_launch_fwd_desc(&dp, (void *)s);
-	mosrx__note_stream(c, s);
-	return rc;
-}
-
-/* MOSRX_OP_FWD_DESC under mosrx_set_fwd_one's limit: mosrx_fwd_plan_dev and
- * mosrx_fwd_desc_rings_dev on one batch, their refusals in their order, as one
- * launch. */
-static int fwd_plan_desc_one(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, int in_ifidx,
-                             mosrx_fwd *d_plan, uint32_t nrings, uint32_t *d_tx_src, uint16_t *d_tx_len,
-                             uint32_t *d_tx_mac, mosrx_fwd_ring *d_rings, void *d_scratch, size_t scratch_bytes,
-                             hipStream_t s)
-{
-	mosrx_fparams fp;
-	mosrx_dparams dp;
-	int rc;
-	if (!c || !b || !d_plan || ((uintptr_t)d_plan & 7) || (rec_bytes != 8 && rec_bytes != 16) || in_ifidx < 0 ||
-	    in_ifidx >= MOSRX_FWD_MAX_NETDEVS || (b->n && (!d_rec || ((uintptr_t)d_rec & (uintptr_t)(rec_bytes - 1)))))
-		return -EINVAL;
-	if ((rc = fwd_batch(c, b, &fp)))
-		return rc;
-	if (!c->d_fwd)
-		return -ENOENT;
-	if (!d_tx_src || ((uintptr_t)d_tx_src & 3) || !d_tx_len || ((uintptr_t)d_tx_len & 1) || !d_tx_mac ||
-	    ((uintptr_t)d_tx_mac & 3) || !d_rings || ((uintptr_t)d_rings & 15) || !d_scratch || ((uintptr_t)d_scratch & 15) ||
-	    nrings < 1 || nrings > MOSRX_FWD_MAX_NETDEVS || scratch_bytes < mosrx_fwd_desc_scratch_bytes(b->n, nrings) ||
-	    nrings < c->fwd_num_netdevs)
-		return -EINVAL;
-	if (!s)
-		s = c->stream;
-	fp.rec = (const uint8_t *)d_rec;
-	fp.rec_bytes = (uint32_t)rec_bytes;
-	fp.in_ifidx = in_ifidx;
-	memset(&dp, 0, sizeof(dp));
-	dp.frames = fp.frames;
-	dp.off = fp.off;
-	dp.tab = fp.tab;
-	dp.plan = d_plan;
-	dp.frames_bytes = fp.frames_bytes;
-	dp.n = fp.n;
-	dp.nrings = nrings;
-	dp.tx_src = d_tx_src;
-	dp.tx_len = d_tx_len;
-	dp.tx_mac = d_tx_mac;
-	dp.rings = d_rings;
-	HIPCHK(hipSetDevice(c->device));
-	fwd_mark_used(c);
-	rc = fwd_one_batch(c, &dp, &fp, s);
-	mosrx__note_stream(c, s);
-	return rc;
-}
-
-int mosrx_queue_set_fwd_desc(mosrx_ctx *c, mosrx_queue *q, const mosrx_queue_fwd_desc *f)
-{
-	mosrx_fdesc *h;
-	mosrx_ddesc *g;
-	uint32_t i, tiles = 0, maxn = 0;
-	size_t rows;
-	if (!c || !q)
-		return -EINVAL;
-	if (!f) {
-		if (q->fwd_desc)
-			q->fwd = q->fwd_desc = 0;
-		return 0;
-	}
-	if (q->fwd && !q->fwd_desc)   /* mosrx_queue_set_fwd's attachment is in place */
-		return -EINVAL;
-	if (!f->d_plan || !f->d_tx_src || !f->d_tx_len || !f->d_tx_mac || !f->d_rings || f->nrings < 1 ||
-	    f->nrings > MOSRX_FWD_MAX_NETDEVS)
-		return -EINVAL;
-	for (i = 0; i < q->nb; i++) {
-		if (f->in_ifidx && f->in_ifidx[i] >= MOSRX_FWD_MAX_NETDEVS)
-			return -EINVAL;
-		if (!f->d_rings[i] || ((uintptr_t)f->d_rings[i] & 15))
-			return -EINVAL;
-		if (!q->h_desc[i].n)
-			continue;
-		if (!f->d_plan[i] || ((uintptr_t)f->d_plan[i] & 7) || ((uintptr_t)q->h_desc[i].off & 3) ||
-		    ((uintptr_t)q->h_desc[i].len & 1) || !f->d_tx_src[i] || ((uintptr_t)f->d_tx_src[i] & 3) || !f->d_tx_len[i] ||
-		    ((uintptr_t)f->d_tx_len[i] & 1) || !f->d_tx_mac[i] || ((uintptr_t)f->d_tx_mac[i] & 3))
-			return -EINVAL;
-	}
-	h = calloc(q->nb, sizeof(*h));
-	g = calloc(q->nb, sizeof(*g));
-	if (!h || !g) {
-		free(h);
-		free(g);
-		return -ENOMEM;
-	}
-	for (i = 0; i < q->nb; i++) {
-		const mosrx_qdesc *d = &q->h_desc[i];
-		h[i].n = g[i].n = d->n;
-		h[i].tile_base = g[i].tile_base = tiles;
-		h[i].in_ifidx = f->in_ifidx ? f->in_ifidx[i] : 0;
-		h[i].rings = g[i].rings = f->d_rings[i];
-		tiles += (d->n + MOSRX_FWD_TILE - 1) / MOSRX_FWD_TILE;
-		if (d->n > maxn)
-			maxn = d->n;
-		if (!d->n)
-			continue;
-		h[i].frames = g[i].frames = d->frames;
-		h[i].off = g[i].off = d->off;
-		h[i].len = d->len;
-		h[i].rec = (const uint8_t *)d->out;
-		h[i].frames_bytes = g[i].frames_bytes = d->frames_bytes;
-		h[i].plan = f->d_plan[i];
-		g[i].plan = f->d_plan[i];
-		g[i].tx_src = f->d_tx_src[i];
-		g[i].tx_len = f->d_tx_len[i];
-		g[i].tx_mac = f->d_tx_mac[i];
-	}
-	/* from here a failure leaves the queue without forwarding, as mosrx_queue_set_fwd's does */
-	q->fwd = q->fwd_build = q->fwd_desc = 0;
-	rows = ((size_t)tiles ? tiles : 1) * f->nrings;
-	if (hipSetDevice(c->device) != hipSuccess) {
-		free(h);
-		free(g);
-		return -EIO;
-	}
-	if (rows > q->fscratch_rows) {
-		if (q->d_fscratch)
-			hipFree(q->d_fscratch);
-		q->d_fscratch = NULL;
-		q->fscratch_rows = 0;
-		if (hipMalloc((void **)&q->d_fscratch, rows * MOSRX_FWD_ROW) != hipSuccess) {
-			free(h);
-			free(g);
-			return -ENOMEM;
-		}
-		q->fscratch_rows = rows;
-	}
-	if ((!q->d_fdesc && hipMalloc((void **)&q->d_fdesc, (size_t)q->nb * sizeof(*h)) != hipSuccess) ||
-	    (!q->d_ddesc && hipMalloc((void **)&q->d_ddesc, (size_t)q->nb * sizeof(*g)) != hipSuccess)) {
-		free(h);
-		free(g);
-		return -ENOMEM;
-	}
-	if (hipMemcpy(q->d_fdesc, h, (size_t)q->nb * sizeof(*h), hipMemcpyHostToDevice) != hipSuccess ||
-	    hipMemcpy(q->d_ddesc, g, (size_t)q->nb * sizeof(*g), hipMemcpyHostToDevice) != hipSuccess) {
-		free(h);
-		free(g);
-		return -EIO;
-	}
-	free(h);
-	free(g);
-	q->fwd_tiles = tiles;
-	q->fwd_nrings = f->nrings;
-	q->fwd_cap_units = 0;
-	q->fwd_maxn = maxn;
-	q->fwd_desc = 1;
-	q->fwd = 1;
 	return 0;
 }

@@ -1,6 +1,6 @@
 /*
  * mosrx_ctx.h — host-side context layout shared by the C host files
- * (mosrx_api.c, bpf_api.c).  Not part of the ABI.
+ * (mosrx_api.c, bpf_api.c, fwd_api.c).  Not part of the ABI.
  */
 #ifndef MOSRX_CTX_H
 #define MOSRX_CTX_H
@@ -179,6 +179,48 @@ struct mosrx_ctx {
 	uint32_t fwd_tmp_n, fwd_tmp_rings;
 };
 
+/* ---- batch queue (one launch over many resident batches) ---- */
+struct mosrx_queue {
+	mosrx_qdesc *d_desc;
+	mosrx_qdesc *h_desc;   /* host copy: the per-batch BPF launches of a queue with masks */
+	uint32_t nb;
+	uint32_t total_tiles;
+	uint32_t tpb;   /* tiles per batch if uniform, else 0 */
+	int tile;
+	uint64_t bytes, n;   /* frame bytes and frames of all batches (tail policy) */
+	int compact;         /* 8-byte records */
+	int uni;             /* some batch carries a layout hint */
+	int match;           /* the descriptors' bmatch: the installed BPF set's masks */
+	uint32_t **d_match;  /* per batch (the non-fused form) */
+	/* queue steering (mosrx_queue_set_steer): the batches' steer table and the
+	 * histogram rows, allocated at the first attach; steer: outputs attached */
+	mosrx_sdesc *d_sdesc;
+	uint32_t *d_shist;
+	uint32_t steer_tiles;
+	uint32_t steer_maxn;   /* the largest batch, kept at attach: a run takes the one-launch form by it */
+	int steer;
+	/* its gather form (mosrx_queue_set_steer_gather): the table parallel to
+	 * d_sdesc; gather: the scatter pass of a run is the gather form */
+	mosrx_gdesc *d_gdesc;
+	int gather;
+	/* ... and its side form (mosrx_queue_set_steer_gather_side), the third table */
+	mosrx_xdesc *d_xdesc;
+	int side;
+	/* forwarding (mosrx_queue_set_fwd): the batches' table and the build's
+	 * scratch rows, allocated at the first attach that needs them; fwd: a plan
+	 * attached, fwd_build: with the ring build */
+	mosrx_fdesc *d_fdesc;
+	uint32_t *d_fscratch;
+	size_t fscratch_rows;
+	uint32_t fwd_tiles, fwd_nrings, fwd_cap_units;
+	int fwd, fwd_build;
+	/* its descriptor form (mosrx_queue_set_fwd_desc): the store launch's table,
+	 * parallel to d_fdesc; fwd_desc: attached (then fwd is set, fwd_build is not) */
+	mosrx_ddesc *d_ddesc;
+	int fwd_desc;
+	uint32_t fwd_maxn;   /*   its largest batch: what mosrx_set_fwd_one's limit is held against */
+};
+
 int mosrx__check_batch(const mosrx_batch *b, int dev);
 void *mosrx__host_dev_of(const void *p, uint64_t len, int device);
 int mosrx__bpf_jit_request(mosrx_ctx *c, const mosrx_bpf_insn *insns);
@@ -215,5 +257,49 @@ int mosrx__drain(mosrx_ctx *c);
  * tail loads cached instead of non-temporal for batches of small frames when
  * the context runs the library default (mosrx_api.c). */
 int mosrx__tail_variant(const mosrx_ctx *c, uint64_t bytes, uint64_t n);
+
+/* ---- forwarding's host side (fwd_api.c), as mosrx_api.c's flows reach it ---- */
+
+/* What an armed group (mosrx_slot_fwd) needs of the context, at the arm and
+ * again at the submit, since the tables may change in between: -ENOENT with no
+ * tables installed, -EINVAL with fewer rings than the tables have netdevs. */
+int mosrx__fwd_group_check(const mosrx_ctx *c, const mosrx_slot_fwd_out *o);
+/* ... and of batch i's outputs, n its frame count: -EINVAL for an input netdev
+ * out of range, ring rows that are NULL or not 4-byte aligned, or, of a batch
+ * with frames, an array that is NULL or not aligned to its entries. */
+int mosrx__fwd_group_check_batch(const mosrx_slot_fwd_out *o, uint32_t i, uint32_t n);
+/* A group without a frame launches nothing: its nb batches' ring rows, zeroed
+ * on the host, are its whole forwarding output. */
+void mosrx__fwd_group_empty(const mosrx_slot_fwd_out *o, uint32_t nb);
+/* The device addresses of an armed group's forwarding outputs, when every one
+ * of them is pinned and aligned to its stores (ring rows: 16 bytes): into the
+ * slot's two forwarding tables, fd and dd.  1: all are there and the launches
+ * may write in place; 0: the group copies back from the slot's own buffers. */
+int mosrx__fwd_group_outputs(int device, const mosrx_batch *b, uint32_t nb, const mosrx_slot_fwd_out *o, mosrx_fdesc *fd,
+                             mosrx_ddesc *dd);
+/* The plan and descriptor launches of an armed group, behind its classify (and
+ * steer) launches on the slot's stream: over the records and descriptors where
+ * the classify launch wrote and read them (s->h_qdesc), into the caller's
+ * pinned arrays (in_place: mosrx__fwd_group_outputs filled the tables) or the
+ * slot's buffers, which are then copied back per batch -- all n entries of each
+ * array: those at and past the sent count then hold nothing of meaning. */
+int mosrx__fwd_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
+                            const mosrx_slot_fwd_out *o);
+/* A queue's forwarding conditions at run time (mosrx_queue_run asks before it
+ * enqueues anything): -ENOENT with no tables installed, -EINVAL when rings are
+ * attached and are fewer than the tables' netdevs. */
+int mosrx__fwd_queue_check(const mosrx_ctx *c, const mosrx_queue *q);
+/* The attached form's launches behind whatever the run already put on the
+ * stream: the plan alone, the plan and the byte-ring build's three, or the
+ * descriptor form's four -- or its one (mosrx_set_fwd_one). */
+int mosrx__fwd_queue_launch(mosrx_ctx *c, const mosrx_queue *q, void *stream);
+/* mosrx_time_op's block of TX outputs and scratch for the forwarding op `op`
+ * over these batches (MOSRX_OP_FWD_PLAN needs none), kept by the context and
+ * only grown; -ENOENT for a ring op with no tables installed. */
+int mosrx__fwd_tmp_reserve(mosrx_ctx *c, int op, const mosrx_batch *b, uint32_t nb);
+/* One enqueue of a forwarding op on batch b for mosrx_time_op: the plan from
+ * the records in `out` (arg: rec_bytes | in_ifidx << 8) into `aux`, then the
+ * op's build into stream s's part of that block. */
+int mosrx__fwd_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out, void *aux, hipStream_t s);
 
 #endif

@@ -1,5 +1,5 @@
 /*
- * mosrx_fwd.h — shared between the C host library (mosrx_api.c) and the
+ * mosrx_fwd.h — shared between the C host library (fwd_api.c) and the
  * forwarding kernels (mosrx_fwd.hip).  Plain C layout.  Kept out of
  * mosrx_internal.h, which is embedded for hipRTC: the fused kernels' source
  * does not change with it.
