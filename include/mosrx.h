@@ -654,6 +654,110 @@ uint32_t mosrx_get_fwd_one(const mosrx_ctx *c);
 /* Forwarding launches of this context that took the one-launch form so far (n == 0 launches included). */
 uint64_t mosrx_fwd_one_count(const mosrx_ctx *c);
 
+/* ---- firewall rules on SYN frames, ahead of forwarding ------------------------- */
+/* What samples/simple_firewall does to the frames a forward = 1 stack passes
+ * on: on a TCP frame with SYN and no ACK (CatchInitSYN, simple_firewall.c:362-372)
+ * it walks its rules, first match wins (FWRLookup, :307-330, over MatchAddr /
+ * MatchPort, :291-305), counts the hit in the rule (fr_count) and, for a DROP
+ * rule, withholds that frame from forwarding (ApplyActionPerFlow, :332-360:
+ * mtcp_setlastpkt(MOS_DROP)).  Here as one launch over a classified batch,
+ * between the plan launch and the build launches: stateless per frame.
+ *
+ * A frame is looked up when its record's reason is TCP_OK or TCP_LEN_OK, the
+ * context has num_msp != 0 and the listener flag off (the TCP arm of
+ * mosrx_mos_forwards), its tcp_flags have SYN and not ACK, and its IPv4 packet
+ * lies inside its capture (the plan's condition).  `forward` is no condition:
+ * the sample looks up and counts either way.  The key is read from the frame
+ * as the sample reads it: saddr / daddr at bytes 26..33, the ports at
+ * 14 + 4 * ihl (ihl from byte 14), each the raw value of a little-endian host;
+ * a key byte at or past the batch buffer's end (rounded up to 16) reads zero.
+ *
+ * The boundary: mOS raises the sample's event from inside its stream engine,
+ * behind tcp.c:445.  Where that engine would not raise MOS_ON_PKT_IN for an
+ * accepted SYN (a retransmitted SYN of a flow it no longer monitors, say), the
+ * sample looks nothing up and this launch does.  The ACCEPT branch
+ * (MOS_STOP_MON) does nothing to forwarding and is not modelled. */
+#define MOSRX_ACL_MAX_RULES 1024   /* MAX_RULES */
+enum { MOSRX_ACL_ACCEPT = 1, MOSRX_ACL_DROP = 2 };   /* FRA_ACCEPT, FRA_DROP */
+/* One rule: the fields struct FirewallRule holds after ParseConfigFile, network
+ * order as stored.  src_ip / dst_ip are already masked (ExtractIPAddress,
+ * :204); src_mask / dst_mask are the values IP_NETMASK ands with,
+ * 0xFFFFFFFF >> (32 - bits) on the stored address -- for a prefix that is no
+ * multiple of 8 that keeps the low bits of the last partial octet, which is the
+ * sample's behaviour; no mask is recomputed here.  An address or port of 0 is
+ * the wildcard. */
+typedef struct mosrx_acl_rule {
+	uint32_t src_ip, src_mask, dst_ip, dst_mask;
+	uint16_t sport, dport;
+	uint8_t  action;      /* MOSRX_ACL_ACCEPT or MOSRX_ACL_DROP */
+	uint8_t  pad[3];
+} mosrx_acl_rule;
+/* The kind the launch gives a dropped SYN's plan record: {tx_len 0, out_ifidx -1,
+ * MOSRX_FWD_DROP, arp_idx 0xFFFF, reserved 0}.  Every build sends kinds IP and
+ * ETH only, so the frame falls out of all of them. */
+#define MOSRX_FWD_DROP 6
+/* d_hit values that are no rule index */
+#define MOSRX_ACL_NOT_LOOKED_UP 0xFFFFu
+#define MOSRX_ACL_NO_MATCH      0xFFFEu   /* looked up, no rule matched: the default ACCEPT */
+
+/* 0 when n <= MOSRX_ACL_MAX_RULES and every action is one of the two, else
+ * -EINVAL (also for rules NULL with n != 0).  Needs no GPU. */
+int  mosrx_acl_check(const mosrx_acl_rule *rules, uint32_t n);
+/* Validate the rules (mosrx_acl_check) and upload one packed device copy for
+ * the context; NULL / 0 clears them.  In effect for launches submitted after it
+ * returns; launches already submitted keep the copy they were given (the copies
+ * rotate over a pool, and one a launch may have read is rewritten only after
+ * those launches drained), as mosrx_fwd_set's. */
+int  mosrx_acl_set(mosrx_ctx *c, const mosrx_acl_rule *rules, uint32_t n);
+/* Rules installed (0: none). */
+uint32_t mosrx_acl_count(const mosrx_ctx *c);
+/* The launch over a device-resident batch and its n records of rec_bytes (16 or
+ * 8) as a classify call on the same stream left them:
+ *   d_hit[n]     u16, 2-byte aligned: the index of the rule that matched,
+ *                MOSRX_ACL_NOT_LOOKED_UP or MOSRX_ACL_NO_MATCH
+ *   d_counts[MOSRX_ACL_MAX_RULES]  u32, optional: one added per hit (atomic adds:
+ *                a sum, so the order does not matter); the caller zeroes it, and
+ *                launches into the same array accumulate
+ *   d_plan[n]    optional, 8-byte aligned, as mosrx_fwd_plan_dev on the same
+ *                stream left it: under forward != 0 the record of a frame whose
+ *                rule is DROP becomes the MOSRX_FWD_DROP record above; no other
+ *                record is written (forward = 0: none is, the plan stays NONE)
+ * One launch; allocates nothing, graph-capturable.  The returns in their order:
+ * -EINVAL for a NULL or misaligned pointer or a bad rec_bytes; then -ENOENT with
+ * no rules set, whatever n is (as mosrx_fwd_plan_dev without tables); then, for
+ * n == 0, 0 with nothing launched. */
+int  mosrx_acl_apply_dev(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, mosrx_fwd *d_plan,
+                         uint16_t *d_hit, uint32_t *d_counts, void *stream);
+/* The batch-queue form: d_hit[nb] (one array per batch; of an empty batch it
+ * may be NULL) and d_counts (one array for the queue, or NULL).  mosrx_queue_run
+ * then runs one more launch over all of the queue's batches (a workgroup finds
+ * its batch in a device-resident table; tiles never straddle batches): with
+ * forwarding attached (mosrx_queue_set_fwd / _fwd_desc, before or after this
+ * call) between the plan launch and the build launches, amending the attached
+ * plan arrays; without, behind the classify launch, with no plan.  The
+ * one-launch forwarding form (mosrx_set_fwd_one) plans and builds in one kernel
+ * and leaves no place for this launch: a run with rules attached takes the
+ * multi-launch path whatever that limit is.  A run with no rules installed is
+ * -ENOENT and enqueues nothing.  d_hit NULL detaches. */
+int  mosrx_queue_set_acl(mosrx_ctx *c, mosrx_queue *q, uint16_t *const *d_hit, uint32_t *d_counts);
+/* The slot arm: the next host group submit on `slot` runs the firewall launch
+ * over the group's batches, behind its classify (and steer) launches -- with
+ * mosrx_slot_fwd armed too, between the group's plan launch and its descriptor
+ * build, amending the group's plan (such a group takes the multi-launch path
+ * whatever mosrx_set_fwd_one says: the one launch leaves no place for this
+ * one); alone, with no plan.  h_hit[nb]: host arrays of the batches' n u16
+ * entries (of an empty batch it may be NULL); h_counts: a host array of
+ * MOSRX_ACL_MAX_RULES u32 the group's hits are added to, or NULL.  The hit
+ * arrays are written in place for a direct group whose outputs are all pinned
+ * and aligned, and copied back otherwise -- the forwarding arm's rule, decided
+ * together with it; h_counts is added to in place when it is pinned, else
+ * through a copy in and out.  Both are complete when the slot's wait returns.
+ * h_hit NULL disarms.  -EBUSY: the slot is in flight; -ENOENT: no rules set (at
+ * the arm, and again at the submit); -EINVAL at the submit for a hit array that
+ * is NULL or odd of a batch with frames.  Taken by the next group submit on the
+ * slot whatever becomes of it. */
+int  mosrx_slot_acl(mosrx_ctx *c, int slot, uint16_t *const *h_hit, uint32_t *h_counts);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned
@@ -827,7 +931,10 @@ enum { MOSRX_OP_CLASSIFY = 0, MOSRX_OP_CLASSIFY_FH = 1, MOSRX_OP_BPF = 2, MOSRX_
                                 * what the batch's frames need at most, nrings the tables' num_netdevs */,
        MOSRX_OP_FWD_DESC = 13 /* MOSRX_OP_FWD_PLAN followed by the descriptor form of the ring build (-ENOTSUP from
                                * mosrx_time_op_dispatch); outputs and scratch are the timing call's own, nrings the
-                               * tables' num_netdevs */ };
+                               * tables' num_netdevs */,
+       MOSRX_OP_ACL = 14 /* the firewall launch (mosrx_acl_apply_dev) over records already made: out[i] the records
+                          * of batch i, aux[i] its u16 hit array, `arg` = rec_bytes; no plan and no counts.  Not a
+                          * kernel of the classify object: -ENOTSUP from mosrx_time_op_dispatch */ };
 int  mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t nb, void *const *out,
                    void *const *aux, uint32_t iters, uint32_t nstreams, float *total_ms, float *avg_kernel_ms);
 /* The kernel's own duration, averaged over `iters` back-to-back launches on

@@ -141,6 +141,19 @@ typedef struct mosrx_fwd_view {
 	const uint32_t *tx_mac;      /* 3 dwords an entry */
 	const mosrx_fwd_ring *rings; /* nrings */
 } mosrx_fwd_view;
+#define MOSRX_PKT_RX_ACL     0x1D   /* argp: mosrx_acl_view * -- the exposed batch's firewall hits and the
+                                     * counts so far (mosrx_gpu_module_set_acl; -1 without it, and wherever
+                                     * MOSRX_PKT_RX_FWD answers -1 with forwarding on) */
+/* hit[i]: the rule that matched frame i, MOSRX_ACL_NOT_LOOKED_UP or
+ * MOSRX_ACL_NO_MATCH (mosrx_acl_apply_dev); counts[r]: hits of rule r over every
+ * group of the netdev waited for so far, this batch's group included (a batch
+ * classified again after a parameter change is counted once, at its first
+ * launch).  Valid until the next recv_pkts on the netdev. */
+typedef struct mosrx_acl_view {
+	uint32_t n, nrules;
+	const uint16_t *hit;         /* n */
+	const uint32_t *counts;      /* MOSRX_ACL_MAX_RULES */
+} mosrx_acl_view;
 typedef struct mosrx_rx_state {
 	uint32_t num_msp, num_esp;   /* the stack state of the batch's verdicts */
 	uint32_t gen;                /* the netdev's parameter / filter generation they were made with */
@@ -590,6 +603,15 @@ int mosrx_backend_forward(const io_module_func *iom, struct mtcp_thread_context 
  * takes the group path.  NULL turns forwarding off (the default).  -EINVAL for
  * tables mosrx_fwd_set refuses: the setting stays as it was. */
 int mosrx_gpu_module_set_fwd(const mosrx_fwd_tables *t, int listener);
+/* The firewall rules (mosrx_acl_set) of every context init_handle opens from now
+ * on; every group submit is then armed with mosrx_slot_acl, so with forwarding
+ * on MOSRX_PKT_RX_FWD's rings (and mosrx_backend_forward) already lack the SYNs
+ * a DROP rule matched, and MOSRX_PKT_RX_ACL hands out the hits and counts.  A
+ * group with rules armed takes the multi-launch forwarding path whatever
+ * mosrx_gpu_module_set_fwd_one says.  NULL / 0 turns them off (the default).
+ * -EINVAL for rules mosrx_acl_check refuses: the setting stays as it was.  A
+ * setting of the module, not a field of mosrx_gpu_module_cfg. */
+int mosrx_gpu_module_set_acl(const mosrx_acl_rule *rules, uint32_t n);
 int mosrx_fwd_desc_send(const io_module_func *iom, struct mtcp_thread_context *ctx, const uint8_t *frames,
                         const uint32_t *off, const uint32_t *h_tx_src, const uint16_t *h_tx_len,
                         const uint32_t *h_tx_mac, const mosrx_fwd_ring *h_rings, uint32_t nrings,

@@ -562,6 +562,46 @@ int mosrx__fwd_queue_launch(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 	return rc;
 }
 
+int mosrx__fwd_queue_launch_plan(mosrx_ctx *c, const mosrx_queue *q, void *stream)
+{
+	mosrx_fqparams fq;
+	const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+	int rc;
+	fqparams_fill(c, &fq, q->d_fdesc, q->d_fscratch, q->nb, q->fwd_tiles, q->compact ? 8u : 16u, q->fwd_nrings);
+	HIPCHK(hipSetDevice(c->device));
+	fwd_mark_used(c);
+	rc = mosrx_launch_fwd_queue(&fq, 0, (void *)s);
+	mosrx__note_stream(c, s);
+	return rc;
+}
+
+int mosrx__fwd_queue_launch_build(mosrx_ctx *c, const mosrx_queue *q, void *stream)
+{
+	mosrx_fqparams fq;
+	const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+	int rc;
+	if (!q->fwd_desc && !q->fwd_build)
+		return 0;
+	fqparams_fill(c, &fq, q->d_fdesc, q->d_fscratch, q->nb, q->fwd_tiles, q->compact ? 8u : 16u, q->fwd_nrings);
+	fq.cap_units = q->fwd_cap_units;
+	HIPCHK(hipSetDevice(c->device));
+	fwd_mark_used(c);
+	if (q->fwd_desc) {
+		mosrx_dqparams dq;
+		memset(&dq, 0, sizeof(dq));
+		dq.desc = q->d_ddesc;
+		dq.tab = fq.tab;
+		dq.scratch = fq.scratch;
+		dq.nb = fq.nb;
+		dq.total_tiles = fq.total_tiles;
+		dq.nrings = fq.nrings;
+		rc = mosrx_launch_fwd_desc_queue_build(&fq, &dq, (void *)s);
+	} else
+		rc = mosrx_launch_fwd_queue_build(&fq, (void *)s);
+	mosrx__note_stream(c, s);
+	return rc;
+}
+
 /* What either attach asks of batch i whatever its outputs are: an input netdev
  * in range and, of a batch with frames, its plan array and off[] / len[]
  * aligned to the kernels' loads. */
@@ -777,8 +817,8 @@ int mosrx__fwd_group_outputs(int device, const mosrx_batch *b, uint32_t nb, cons
 	return 1;
 }
 
-int mosrx__fwd_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
-                            const mosrx_slot_fwd_out *o)
+int mosrx__fwd_group_launch_acl(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
+                                const mosrx_slot_fwd_out *o, uint16_t *const *h_hit, uint32_t *h_counts)
 {
 	mosrx_fqparams fq;
 	uint32_t i, tiles = 0, maxn = 0;
@@ -802,8 +842,24 @@ int mosrx__fwd_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, 
 	HIPCHK(hipMemcpyAsync(s->d_ddesc, s->h_ddesc, nb * sizeof(mosrx_ddesc), hipMemcpyHostToDevice, s->stream));
 	fqparams_fill(c, &fq, s->d_fdesc, s->d_fscr, nb, tiles, (uint32_t)rsz, o->nrings);
 	fwd_mark_used(c);
-	if ((rc = fwd_desc_queue_launch(c, &fq, s->d_ddesc, maxn, (void *)s->stream)))
-		return rc;
+	if (!h_hit) {
+		if ((rc = fwd_desc_queue_launch(c, &fq, s->d_ddesc, maxn, (void *)s->stream)))
+			return rc;
+	} else {
+		/* the firewall launch between the plan and the build: never the one-launch form */
+		mosrx_dqparams dq;
+		memset(&dq, 0, sizeof(dq));
+		dq.desc = s->d_ddesc;
+		dq.tab = fq.tab;
+		dq.scratch = fq.scratch;
+		dq.nb = fq.nb;
+		dq.total_tiles = fq.total_tiles;
+		dq.nrings = fq.nrings;
+		if ((rc = mosrx_launch_fwd_queue(&fq, 0, (void *)s->stream)) ||
+		    (rc = mosrx__acl_group_launch(c, s, b, nb, rsz, in_place, 1, h_hit, h_counts)) ||
+		    (rc = mosrx_launch_fwd_desc_queue_build(&fq, &dq, (void *)s->stream)))
+			return rc;
+	}
 	for (i = 0, pre = 0; i < nb; pre += b[i].n, i++) {
 		const size_t n = b[i].n;
 		if (o->h_plan && n && s->h_fdesc[i].plan == s->d_fplan + pre)
@@ -819,6 +875,12 @@ int mosrx__fwd_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, 
 		HIPCHK(hipMemcpyAsync(o->h_tx_mac[i], s->d_ftmac + 3 * pre, n * 12, hipMemcpyDeviceToHost, s->stream));
 	}
 	return 0;
+}
+
+int mosrx__fwd_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
+                            const mosrx_slot_fwd_out *o)
+{
+	return mosrx__fwd_group_launch_acl(c, s, b, nb, rsz, in_place, o, NULL, NULL);
 }
 
 /* ---- the timing ops (mosrx_time_op) ------------------------------------------------- */

@@ -87,6 +87,8 @@ struct stage {
 	uint16_t *ftlen;
 	mosrx_fwd_ring *frings;   /*   and the ring rows */
 	int fwd;                  /* its last launch filled them and nothing has touched the batch since (MOSRX_PKT_RX_FWD) */
+	uint16_t *ahit;           /* pinned, firewall rules (mosrx_gpu_module_set_acl): n hits */
+	int acl;                  /* its last launch filled them, under fwd's conditions (MOSRX_PKT_RX_ACL) */
 	uint32_t n, max_len;
 	uint32_t rec0;            /* its first record's index in the group's record arrays */
 	uint32_t stride;          /* frame i at off[0] + i * stride (a fixed-size packing), else 0: the layout hint */
@@ -122,6 +124,8 @@ struct group {
 	uint32_t *ftsrc, *ftmac;  /*   rec_cap entries of the descriptor rings, */
 	uint16_t *ftlen;
 	mosrx_fwd_ring *frings;   /*   cap_st x MOSRX_FWD_MAX_NETDEVS ring rows */
+	uint16_t *ahit;           /* firewall rules set: rec_cap hits (pinned), */
+	uint32_t *acnt;           /*   and the counts of the group's last submit (not pinned: copied out with the group) */
 	uint64_t rec_cap;         /* frames the record arrays hold */
 	struct stage *st;         /* cap_st stages */
 	uint32_t cap_st;
@@ -137,6 +141,7 @@ struct if_state {
 	uint32_t cur_idx;         /* its batch exposed now */
 	int inflight;             /* group being classified, -1 none */
 	uint32_t gen;             /* bumped by SET_PARAMS / SET_BPF: older records are classified again */
+	uint32_t acl_counts[MOSRX_ACL_MAX_RULES];   /* firewall rules: hits per rule of every group waited for so far */
 	/* the latency cap's rates (cfg.group_max_us), EWMAs: a group's submit ->
 	 * records ready per frame byte, and the host's time per frame from a group's
 	 * exposure to the recv_pkts that moves past it (the app's walk + the next
@@ -229,6 +234,27 @@ int mosrx_gpu_module_set_fwd_one(int32_t max_frames)
 }
 
 int32_t mosrx_gpu_module_get_fwd_one(void) { return g_fwd_one; }
+
+/* mosrx_gpu_module_set_acl: the firewall rules every context opened from now on
+ * gets; g_acl_n 0: none */
+static mosrx_acl_rule g_acl[MOSRX_ACL_MAX_RULES];
+static uint32_t g_acl_n;
+
+int mosrx_gpu_module_set_acl(const mosrx_acl_rule *rules, uint32_t n)
+{
+	if (rules && n) {   /* mosrx_acl_set's own rules: a refused setting leaves the one in place */
+		uint32_t i;
+		if (n > MOSRX_ACL_MAX_RULES)
+			return -EINVAL;
+		for (i = 0; i < n; i++)
+			if (rules[i].action != MOSRX_ACL_ACCEPT && rules[i].action != MOSRX_ACL_DROP)
+				return -EINVAL;
+		memcpy(g_acl, rules, (size_t)n * sizeof(*rules));
+	} else if (n)
+		return -EINVAL;
+	g_acl_n = rules ? n : 0;
+	return 0;
+}
 
 /* mosrx_gpu_module_set_fwd: the tables every context opened from now on gets,
  * and whether an end-host socket listens; g_fwd_on 0: forwarding off */
@@ -526,6 +552,8 @@ static void group_free(mosrx_ctx *mc, struct group *g)
 	if (g->ftlen) mosrx_host_free(mc, g->ftlen);
 	if (g->ftmac) mosrx_host_free(mc, g->ftmac);
 	if (g->frings) mosrx_host_free(mc, g->frings);
+	if (g->ahit) mosrx_host_free(mc, g->ahit);
+	free(g->acnt);
 	free(g->st);
 	memset(g, 0, sizeof(*g));
 }
@@ -610,7 +638,9 @@ static int group_alloc_sized(mosrx_ctx *mc, struct group *g, uint64_t bytes)
 	                  mosrx_host_alloc(mc, g->rec_cap * 2, (void **)&g->ftlen) ||
 	                  mosrx_host_alloc(mc, g->rec_cap * 12, (void **)&g->ftmac) ||
 	                  mosrx_host_alloc(mc, (size_t)g->cap_st * MOSRX_FWD_MAX_NETDEVS * sizeof(mosrx_fwd_ring),
-	                                   (void **)&g->frings))))
+	                                   (void **)&g->frings))) ||
+	    (g_acl_n && (mosrx_host_alloc(mc, g->rec_cap * 2, (void **)&g->ahit) ||
+	                 !(g->acnt = calloc(MOSRX_ACL_MAX_RULES, 4)))))
 		return -ENOMEM;
 	return 0;
 }
@@ -705,6 +735,11 @@ static void gpu_init_handle(struct mtcp_thread_context *ctx)
 		/* mosrx_gpu_module_set_fwd: the context's tables; every group submit is then armed */
 		if (g_fwd_on && ((rc = mosrx_fwd_set(is->mc, &g_fwd)) || (rc = mosrx_fwd_set_listener(is->mc, g_fwd_listener)))) {
 			fprintf(stderr, "[mosrx] gpu_module: mosrx_fwd_set: %s\n", mosrx_strerror(rc));
+			exit(EXIT_FAILURE);
+		}
+		/* mosrx_gpu_module_set_acl: the context's rules; every group submit is then armed */
+		if (g_acl_n && (rc = mosrx_acl_set(is->mc, g_acl, g_acl_n))) {
+			fprintf(stderr, "[mosrx] gpu_module: mosrx_acl_set: %s\n", mosrx_strerror(rc));
 			exit(EXIT_FAILURE);
 		}
 		is->src = (cpu < MAX_THREADS && g_src_cpu[cpu][i]) ? g_src_cpu[cpu][i] : g_cfg.src[i];
@@ -877,6 +912,8 @@ static void group_fill(struct if_state *is, struct group *g)
 		s->ftmac = g->ftmac ? g->ftmac + 3 * recs : NULL;
 		s->frings = g->frings ? g->frings + (size_t)i * MOSRX_FWD_MAX_NETDEVS : NULL;
 		s->fwd = 0;
+		s->ahit = g->ahit ? g->ahit + recs : NULL;
+		s->acl = 0;
 		if (!s->n)
 			break;
 		g->nst++;
@@ -966,6 +1003,9 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	mosrx_fwd_ring *fr[MOSRX_MAX_GROUP];
 	uint8_t fi[MOSRX_MAX_GROUP];
 	const int fwd = g_fwd_on && g->fplan && g->frings;
+	/* firewall rules set: every group is armed with its hits and the group's counts */
+	uint16_t *ah[MOSRX_MAX_GROUP];
+	const int acl = g_acl_n && g->ahit && g->acnt;
 	const int gather = g_cfg.steer >= 2 && g->sqrec;
 	/* cfg.steer = 3: the side arrays this submit makes are gathered with the records */
 	const int side = gather && g_cfg.steer == 3;
@@ -1006,6 +1046,8 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 		fr[i - first] = s->frings;
 		fi[i - first] = (uint8_t)(is - pv->ifs);
 		s->fwd = fwd;
+		ah[i - first] = s->ahit;
+		s->acl = acl;
 		s->msp = is->params.num_msp;
 		s->esp = is->params.num_esp;
 		s->gen = is->gen;
@@ -1029,6 +1071,16 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 			return -1;
 		}
 	}
+	if (acl) {
+		memset(g->acnt, 0, MOSRX_ACL_MAX_RULES * 4);
+		if (mosrx_slot_acl(is->mc, k, ah, g->acnt)) {
+			if (g_cfg.steer)
+				mosrx_slot_steer(is->mc, k, NULL, NULL);
+			if (fwd)
+				mosrx_slot_fwd(is->mc, k, NULL);
+			return -1;
+		}
+	}
 	if (compact && is->nprog)   /* 8-byte records + the set's masks: the fused kernel's 8-byte form */
 		rc = mosrx_classify_host_group_submit_bpf_c8(is->mc, k, b, nb, out8, g_cfg.flowhash ? fh : NULL, mt);
 	else if (compact)
@@ -1039,7 +1091,7 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 	 * the kernel takes the batch as arguments); with cfg.direct_kb a lone batch
 	 * takes the group path, which can run it with no copies (and with cfg.steer,
 	 * since the group submits are the steered ones) */
-	else if (nb == 1 && !g_cfg.flowhash && !g_cfg.direct_kb && !g_cfg.steer && !fwd)
+	else if (nb == 1 && !g_cfg.flowhash && !g_cfg.direct_kb && !g_cfg.steer && !fwd && !acl)
 		rc = mosrx_classify_host_submit_ex(is->mc, k, &b[0], out[0], ti[0]);
 	else
 		rc = mosrx_classify_host_group_submit_ex(is->mc, k, b, nb, out, g_cfg.tcpinfo ? ti : NULL,
@@ -1048,6 +1100,8 @@ static int group_submit(struct gpu_priv *pv, struct if_state *is, int k, uint32_
 		mosrx_slot_steer(is->mc, k, NULL, NULL);
 	if (rc && fwd)
 		mosrx_slot_fwd(is->mc, k, NULL);
+	if (rc && acl)
+		mosrx_slot_acl(is->mc, k, NULL, NULL);
 	return rc;
 }
 
@@ -1061,6 +1115,9 @@ static int group_wait(struct gpu_priv *pv, struct if_state *is, int k, int count
 		pv->stats.rx_batches += is->g[k].nst;
 		for (i = 0; i < is->g[k].nst; i++)
 			pv->stats.rx_frames += is->g[k].st[i].n;
+		/* the group's firewall hits, once: a batch classified again (count 0) was counted at its first launch */
+		for (i = 0; g_acl_n && is->g[k].acnt && i < MOSRX_ACL_MAX_RULES; i++)
+			is->acl_counts[i] += is->g[k].acnt[i];
 	}
 	if (mosrx_last_kernel_ms(is->mc, &ms) == 0) {
 		pv->stats.kernel_ms += ms;
@@ -1455,6 +1512,16 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 		v->rings = s->frings;
 		return 0;
 	}
+	case MOSRX_PKT_RX_ACL: {
+		mosrx_acl_view *v = argp;
+		if (!g_acl_n || !s || !s->acl || (g_fwd_on && !s->fwd))
+			return -1;
+		v->n = s->n;
+		v->nrules = g_acl_n;
+		v->hit = s->ahit;
+		v->counts = pv->ifs[nif].acl_counts;
+		return 0;
+	}
 	case MOSRX_PKT_RX_TCPINFO:
 		if (!s || !s->has_ti)
 			return -1;
@@ -1472,7 +1539,7 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 		/* the exposed batch's plan was made under the old forward / num_msp: the
 		 * caller falls back to its per-frame path for it (MOSRX_PKT_RX_FWD is -1) */
 		if (s)
-			pv->ifs[nif].g[pv->ifs[nif].cur].st[pv->ifs[nif].cur_idx].fwd = 0;
+			pv->ifs[nif].g[pv->ifs[nif].cur].st[pv->ifs[nif].cur_idx].fwd = pv->ifs[nif].g[pv->ifs[nif].cur].st[pv->ifs[nif].cur_idx].acl = 0;
 		return 0;
 	case MOSRX_PKT_SET_BPF:
 		return set_bpf(pv, &pv->ifs[nif], (const mosrx_bpf_set_arg *)argp);
@@ -1497,7 +1564,7 @@ static int32_t gpu_dev_ioctl(struct mtcp_thread_context *ctx, int nif, int cmd, 
 		/* the exposed batch was touched: its forwarding view is withdrawn (the
 		 * caller's per-frame path serves it); the group's later batches keep
 		 * the plans this launch made for them */
-		is->g[is->cur].st[is->cur_idx].fwd = 0;
+		is->g[is->cur].st[is->cur_idx].fwd = is->g[is->cur].st[is->cur_idx].acl = 0;
 		return rc;
 	}
 	case DRV_NAME:

@@ -218,6 +218,10 @@ int mosrx_open(int device, const mosrx_params *p, mosrx_ctx **out)
 		                  hipHostMallocDefault) != hipSuccess ||
 		    hipMalloc((void **)&c->slot[i].d_frings,
 		              (size_t)MOSRX_MAX_GROUP * MOSRX_FWD_MAX_NETDEVS * sizeof(mosrx_fwd_ring)) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_adesc, MOSRX_MAX_GROUP * sizeof(mosrx_adesc)) != hipSuccess ||
+		    hipHostMalloc((void **)&c->slot[i].h_adesc, MOSRX_MAX_GROUP * sizeof(mosrx_adesc),
+		                  hipHostMallocDefault) != hipSuccess ||
+		    hipMalloc((void **)&c->slot[i].d_acnt, MOSRX_ACL_MAX_RULES * 4) != hipSuccess ||
 		    hipMalloc((void **)&c->slot[i].d_cnt, MOSRX_CNT_WORDS * 4) != hipSuccess ||
 		    hipHostMalloc((void **)&c->slot[i].h_cnt, MOSRX_CNT_WORDS * 4, hipHostMallocDefault) != hipSuccess ||
 		    !(c->slot[i].h_prev = calloc(MOSRX_CNT_WORDS, 4))) {
@@ -261,6 +265,8 @@ static void slot_free(struct slot *s)
 	if (s->d_ftlen) hipFree(s->d_ftlen);
 	if (s->d_ftmac) hipFree(s->d_ftmac);
 	if (s->d_fscr) hipFree(s->d_fscr);
+	if (s->d_ahit) hipFree(s->d_ahit);
+	s->d_ahit = NULL;
 	s->d_fplan = NULL; s->d_ftsrc = NULL; s->d_ftlen = NULL; s->d_ftmac = NULL; s->d_fscr = NULL;
 	s->d_sqfh = NULL; s->d_sqmt = NULL; s->d_sqti = NULL;
 	s->d_sidx = NULL; s->d_shist = NULL;
@@ -307,6 +313,9 @@ void mosrx_close(mosrx_ctx *c)
 		if (c->slot[i].d_ddesc) hipFree(c->slot[i].d_ddesc);
 		if (c->slot[i].h_ddesc) hipHostFree(c->slot[i].h_ddesc);
 		if (c->slot[i].d_frings) hipFree(c->slot[i].d_frings);
+		if (c->slot[i].d_adesc) hipFree(c->slot[i].d_adesc);
+		if (c->slot[i].h_adesc) hipHostFree(c->slot[i].h_adesc);
+		if (c->slot[i].d_acnt) hipFree(c->slot[i].d_acnt);
 		if (c->slot[i].d_cnt) hipFree(c->slot[i].d_cnt);
 		if (c->slot[i].h_cnt) hipHostFree(c->slot[i].h_cnt);
 		free(c->slot[i].h_prev);
@@ -320,6 +329,7 @@ void mosrx_close(mosrx_ctx *c)
 	for (i = 0; i < MOSRX_FWD_POOL; i++)
 		if (c->d_fwd_pool[i])
 			hipFree(c->d_fwd_pool[i]);
+	mosrx__acl_free(c);
 	for (i = 0; i < MOSRX_BPF_POOL; i++)
 		if (c->d_bpf_pool[i])
 			hipFree(c->d_bpf_pool[i]);
@@ -702,7 +712,8 @@ int mosrx__slot_reserve(mosrx_ctx *c, struct slot *s, uint64_t frames_bytes, uin
 		    hipMalloc((void **)&s->d_ftsrc, (size_t)nn * 4) != hipSuccess ||
 		    hipMalloc((void **)&s->d_ftlen, (size_t)nn * 2) != hipSuccess ||
 		    hipMalloc((void **)&s->d_ftmac, (size_t)nn * 12) != hipSuccess ||
-		    hipMalloc((void **)&s->d_fscr, fwd_group_scratch(nn)) != hipSuccess) {
+		    hipMalloc((void **)&s->d_fscr, fwd_group_scratch(nn)) != hipSuccess ||
+	    hipMalloc((void **)&s->d_ahit, (size_t)nn * 2) != hipSuccess) {
 			slot_free(s);
 			return -ENOMEM;
 		}
@@ -1292,7 +1303,9 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	struct gather_out go;
 	const uint32_t *msrc[MOSRX_MAX_GROUP];
 	mosrx_slot_fwd_out fo;
-	int fwd;
+	int fwd, acl;
+	uint16_t *const *h_ahit;
+	uint32_t *h_acnt;
 	if (!c || slot < 0 || slot >= NSLOT || !b || !h_out || nb == 0 || nb > MOSRX_MAX_GROUP ||
 	    (h_match && h_tcpinfo) || (compact && h_tcpinfo))
 		return -EINVAL;
@@ -1315,12 +1328,21 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	fwd = s->fwd_armed;
 	fo = s->fwd;
 	s->fwd_armed = 0;
+	/* ... and mosrx_slot_acl: so may the rules */
+	acl = s->acl_armed;
+	h_ahit = s->acl_hit;
+	h_acnt = s->acl_counts;
+	s->acl_armed = 0;
 	if (fwd && (rc = mosrx__fwd_group_check(c, &fo)))
+		return rc;
+	if (acl && (rc = mosrx__acl_group_check(c)))
 		return rc;
 	for (i = 0; i < nb; i++) {
 		if ((rc = mosrx__check_batch(&b[i], 0)))
 			return rc;
 		if (fwd && (rc = mosrx__fwd_group_check_batch(&fo, i, b[i].n)))
+			return rc;
+		if (acl && (rc = mosrx__acl_group_check_batch(h_ahit, i, b[i].n)))
 			return rc;
 		if (b[i].n && (!h_out[i] || (h_tcpinfo && !h_tcpinfo[i]) || (h_fhash && !h_fhash[i]) ||
 		               (h_match && !h_match[i]) ||
@@ -1358,14 +1380,15 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	             (!h_sidx || steer_outputs(c->device, b, nb, h_sidx, h_sqs, s->h_sdesc)) &&
 	             (!go.qrec || gather_outputs(c->device, b, nb, rsz, &go, s->h_gdesc)) &&
 	             (!GATHER_SIDE(&go) || side_outputs(c->device, b, nb, &go, s->h_xdesc)) &&
-	             (!fwd || mosrx__fwd_group_outputs(c->device, b, nb, &fo, s->h_fdesc, s->h_ddesc));
+	             (!fwd || mosrx__fwd_group_outputs(c->device, b, nb, &fo, s->h_fdesc, s->h_ddesc)) &&
+	             (!acl || mosrx__acl_group_outputs(c->device, s, b, nb, h_ahit));
 	if (!direct) {
 		group_copy(s, r, nr, &dev_bytes, 0);
 		if ((rc = mosrx__slot_reserve(c, s, dev_bytes, ntot)))
 			return rc;
 		if ((rc = group_copy(s, r, nr, &dev_bytes, 1)))
 			return rc;
-	} else if ((!out_direct || h_sidx || fwd) && (rc = mosrx__slot_reserve(c, s, 0, ntot))) {
+	} else if ((!out_direct || h_sidx || fwd || acl) && (rc = mosrx__slot_reserve(c, s, 0, ntot))) {
 		return rc;   /* (a steered group's histogram rows are the slot's even when every output is written in place) */
 	}
 	kind = kind_of(c, unknown ? 0 : maxl, dev_bytes, ntot);   /* one shape for the whole group */
@@ -1451,7 +1474,15 @@ static int group_submit(mosrx_ctx *c, int slot, const mosrx_batch *b, uint32_t n
 	s->timed = c->timing;
 	if (h_sidx && (rc = group_steer(c, s, b, nb, rsz, out_direct, h_sidx, h_sqs, &go)))
 		return rc;
-	if (fwd && (rc = mosrx__fwd_group_launch(c, s, b, nb, rsz, out_direct, &fo)))
+	if (fwd && acl)
+		rc = mosrx__fwd_group_launch_acl(c, s, b, nb, rsz, out_direct, &fo, h_ahit, h_acnt);
+	else if (fwd)
+		rc = mosrx__fwd_group_launch(c, s, b, nb, rsz, out_direct, &fo);
+	else if (acl)
+		rc = mosrx__acl_group_launch(c, s, b, nb, rsz, out_direct, 0, h_ahit, h_acnt);
+	else
+		rc = 0;
+	if (rc)
 		return rc;
 	/* results: one copy when the host buffers follow each other, else per batch */
 	for (i = 0, pre = 0; !out_direct && i < nb;) {
@@ -1935,6 +1966,7 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 	case MOSRX_OP_FWD:
 	case MOSRX_OP_FWD_RINGS:
 	case MOSRX_OP_FWD_DESC: return mosrx__fwd_op(c, op, arg, b, out, aux, s);
+	case MOSRX_OP_ACL: return mosrx_acl_apply_dev(c, b, out, arg, NULL, (uint16_t *)aux, NULL, s);
 	default: return -EINVAL;
 	}
 }
@@ -2021,12 +2053,12 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 {
 	int rc;
 	if (!c || !b || nb == 0 || iters == 0 || nstreams == 0 || nstreams > MOSRX_MAX_STREAMS ||
-	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_DESC || (op != MOSRX_OP_TX_CSUM && !out) ||
+	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_ACL || (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
-	      OP_IS_FWD(op)) && !aux) ||
+	      OP_IS_FWD(op) || op == MOSRX_OP_ACL) && !aux) ||
 	    (OP_IS_FWD(op) && (((arg & 0xFF) != 8 && (arg & 0xFF) != 16) || (arg >> 8) < 0 ||
 	                       (arg >> 8) >= MOSRX_FWD_MAX_NETDEVS)) ||
-	    ((op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER) && arg != 8 && arg != 16) ||
+	    ((op == MOSRX_OP_STEER || op == MOSRX_OP_STEER_GATHER || op == MOSRX_OP_ACL) && arg != 8 && arg != 16) ||
 	    (op == MOSRX_OP_STEER_GATHER_SIDE && (((arg & 0xFF) != 8 && (arg & 0xFF) != 16) || (arg >> 8) < 0 || (arg >> 8) > 7)))
 		return -EINVAL;
 	HIPCHK(hipSetDevice(c->device));
@@ -2096,12 +2128,12 @@ int mosrx_time_op_dispatch(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, 
                            void *const *aux, uint32_t iters, float *avg_ms)
 {
 	struct op_run r = {op, arg, b, nb, out, aux};
-	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_DESC ||
+	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_ACL ||
 	    (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
-	      OP_IS_FWD(op)) && !aux))
+	      OP_IS_FWD(op) || op == MOSRX_OP_ACL) && !aux))
 		return -EINVAL;
-	if (OP_IS_STEER(op) || OP_IS_FWD(op))   /* several launches, or none of mosrx_kernels.hip: no dispatch to stamp */
+	if (OP_IS_STEER(op) || OP_IS_FWD(op) || op == MOSRX_OP_ACL)   /* several launches, or none of mosrx_kernels.hip: no dispatch to stamp */
 		return -ENOTSUP;
 	/* (the BPF ops are one launch with the fused kernel / the set's own kernel;
 	 * classify + the set's kernel, two, is refused by the launch count) */
@@ -2356,11 +2388,20 @@ int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 	/* forwarding's run-time conditions first: a run that cannot forward enqueues nothing */
 	if (c && q && q->fwd && (rc = mosrx__fwd_queue_check(c, q)))
 		return rc;
+	if (c && q && q->acl && (rc = mosrx__acl_queue_check(c, q)))
+		return rc;
 	if ((rc = queue_classify(c, q, stream)))
 		return rc;
 	if (q->steer && (rc = queue_steer(c, q, stream)))
 		return rc;
-	return q->fwd ? mosrx__fwd_queue_launch(c, q, stream) : 0;
+	if (!q->acl)
+		return q->fwd ? mosrx__fwd_queue_launch(c, q, stream) : 0;
+	/* the firewall launch between the plan and the build: never the one-launch form */
+	if (q->fwd && (rc = mosrx__fwd_queue_launch_plan(c, q, stream)))
+		return rc;
+	if ((rc = mosrx__acl_queue_launch(c, q, q->fwd, stream)))
+		return rc;
+	return q->fwd ? mosrx__fwd_queue_launch_build(c, q, stream) : 0;
 }
 
 static int queue_set_steer(mosrx_ctx *c, mosrx_queue *q, uint32_t *const *d_idx, uint32_t *const *d_qstart,
@@ -2639,6 +2680,8 @@ void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 		hipFree(q->d_fscratch);
 	if (q->d_ddesc)
 		hipFree(q->d_ddesc);
+	if (q->d_adesc)
+		hipFree(q->d_adesc);
 	free(q->h_desc);
 	free(q->d_match);
 	free(q);

@@ -1,6 +1,6 @@
 /*
  * mosrx_ctx.h — host-side context layout shared by the C host files
- * (mosrx_api.c, bpf_api.c, fwd_api.c).  Not part of the ABI.
+ * (mosrx_api.c, bpf_api.c, fwd_api.c, acl_api.c).  Not part of the ABI.
  */
 #ifndef MOSRX_CTX_H
 #define MOSRX_CTX_H
@@ -11,12 +11,14 @@
 #include "mosrx_internal.h"
 #include "mosrx_steer.h"
 #include "mosrx_fwd.h"
+#include "mosrx_acl.h"
 
 #define HIPCHK(x) do { if ((x) != hipSuccess) return -EIO; } while (0)
 
 #define MOSRX_BPF_JIT_CACHE 16   /* compiled program sets kept per context */
 #define MOSRX_BPF_POOL 8         /* device buffers the interpreter's instructions rotate over */
 #define MOSRX_FWD_POOL 4         /* device copies the forwarding tables rotate over */
+#define MOSRX_ACL_POOL 4         /* device copies the firewall rules rotate over */
 
 /* The fused classify + BPF kernels of a compiled set (bpf_jit.c k_fused_main):
  * one batch as the stream tile (non-temporal / cached tails) or the SMALL tile,
@@ -105,6 +107,15 @@ struct slot {
 	mosrx_fwd *d_fplan;
 	uint32_t *d_ftsrc, *d_ftmac, *d_fscr;
 	uint16_t *d_ftlen;
+	/* the firewall launch of a group (mosrx_slot_acl): the armed outputs (acl_armed;
+	 * taken by the next group submit), the group's batch table (pinned, copied to
+	 * the device per armed submit), hits for cap_n frames and one counts array */
+	uint16_t *const *acl_hit;
+	uint32_t *acl_counts;
+	int acl_armed;
+	mosrx_adesc *h_adesc, *d_adesc;
+	uint16_t *d_ahit;
+	uint32_t *d_acnt;
 	int timed;
 	int busy;
 };
@@ -177,6 +188,13 @@ struct mosrx_ctx {
 	uint8_t *fwd_tmp;
 	size_t fwd_tmp_stride, fwd_tmp_bytes, fwd_tmp_cap;
 	uint32_t fwd_tmp_n, fwd_tmp_rings;
+	/* firewall rules (mosrx_acl_set): the installed rules' device copy (NULL:
+	 * none), one of a pool under the forwarding tables' discipline */
+	mosrx_acl_dev *d_acl;
+	mosrx_acl_dev *d_acl_pool[MOSRX_ACL_POOL];
+	int acl_pool_used[MOSRX_ACL_POOL];
+	uint32_t acl_pool_next;
+	uint32_t acl_n;                  /* the installed rules' count */
 };
 
 /* ---- batch queue (one launch over many resident batches) ---- */
@@ -219,6 +237,13 @@ struct mosrx_queue {
 	mosrx_ddesc *d_ddesc;
 	int fwd_desc;
 	uint32_t fwd_maxn;   /*   its largest batch: what mosrx_set_fwd_one's limit is held against */
+	/* firewall rules (mosrx_queue_set_acl): the batches' table, allocated at the
+	 * first attach, its tile count (the forwarding tables' tile_base[], built the
+	 * same way) and the queue's counts array (NULL: none); acl: attached */
+	mosrx_adesc *d_adesc;
+	uint32_t *acl_counts;
+	uint32_t acl_tiles;
+	int acl;
 };
 
 int mosrx__check_batch(const mosrx_batch *b, int dev);
@@ -285,6 +310,11 @@ int mosrx__fwd_group_outputs(int device, const mosrx_batch *b, uint32_t nb, cons
  * array: those at and past the sent count then hold nothing of meaning. */
 int mosrx__fwd_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
                             const mosrx_slot_fwd_out *o);
+/* The same with the firewall launch armed as well (mosrx_slot_acl): the plan
+ * launch, mosrx__acl_group_launch over the group's plan arrays, then the
+ * descriptor build's three -- never the one launch. */
+int mosrx__fwd_group_launch_acl(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
+                                const mosrx_slot_fwd_out *o, uint16_t *const *h_hit, uint32_t *h_counts);
 /* A queue's forwarding conditions at run time (mosrx_queue_run asks before it
  * enqueues anything): -ENOENT with no tables installed, -EINVAL when rings are
  * attached and are fewer than the tables' netdevs. */
@@ -301,5 +331,36 @@ int mosrx__fwd_tmp_reserve(mosrx_ctx *c, int op, const mosrx_batch *b, uint32_t 
  * the records in `out` (arg: rec_bytes | in_ifidx << 8) into `aux`, then the
  * op's build into stream s's part of that block. */
 int mosrx__fwd_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out, void *aux, hipStream_t s);
+/* The same flows with a queue that has firewall rules attached (q->acl): the
+ * plan launch alone, and the attached build's launches alone (the three of
+ * either ring form; nothing for a plan-only attachment) -- the firewall launch
+ * goes between them, and the one-launch form is not taken. */
+int mosrx__fwd_queue_launch_plan(mosrx_ctx *c, const mosrx_queue *q, void *stream);
+int mosrx__fwd_queue_launch_build(mosrx_ctx *c, const mosrx_queue *q, void *stream);
+
+/* ---- the firewall rules' host side (acl_api.c), as mosrx_api.c's flows reach it ---- */
+
+/* A queue's condition at run time (mosrx_queue_run asks before it enqueues
+ * anything): -ENOENT with no rules installed. */
+int mosrx__acl_queue_check(const mosrx_ctx *c, const mosrx_queue *q);
+/* The one launch over the queue's batches behind whatever the run already put
+ * on the stream; with_plan: the forwarding attachment's plan arrays are amended. */
+int mosrx__acl_queue_launch(mosrx_ctx *c, const mosrx_queue *q, int with_plan, void *stream);
+/* An armed group at the submit: -ENOENT with no rules installed; batch i's hit
+ * array (n its frame count): -EINVAL when NULL or odd and n != 0. */
+int mosrx__acl_group_check(const mosrx_ctx *c);
+int mosrx__acl_group_check_batch(uint16_t *const *h_hit, uint32_t i, uint32_t n);
+/* The device addresses of an armed group's hit arrays into the slot's table,
+ * when every one is pinned: 1, the launch may write in place; 0: copied back. */
+int mosrx__acl_group_outputs(int device, struct slot *s, const mosrx_batch *b, uint32_t nb, uint16_t *const *h_hit);
+/* The launch of an armed group on the slot's stream, over the records and
+ * descriptors where the classify launch wrote and read them (s->h_qdesc);
+ * with_plan: the plan arrays of the slot's forwarding table (s->d_fdesc, filled
+ * by the plan launch ahead of it) are amended.  in_place: mosrx__acl_group_outputs
+ * filled the table; else the slot's hits are copied back per batch. */
+int mosrx__acl_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, uint32_t nb, size_t rsz, int in_place,
+                            int with_plan, uint16_t *const *h_hit, uint32_t *h_counts);
+/* The context's device copies, at close. */
+void mosrx__acl_free(mosrx_ctx *c);
 
 #endif

@@ -197,6 +197,14 @@ _Static_assert(sizeof(mosrx_ddesc) == 72 && sizeof(mosrx_dqparams) == 40, "descr
  * is not looked at.  A queue of empty batches launches the scan alone. */
 int mosrx_launch_fwd_desc_queue(const mosrx_fqparams *fq, const mosrx_dqparams *dq, void *stream);
 
+/* The build launches of the two queue forms without the plan launch ahead of
+ * them (three each: totals, scan, copy / store), for a run that puts a launch
+ * of its own between the plan and the build (the firewall rules,
+ * mosrx_queue_set_acl); the plan alone is mosrx_launch_fwd_queue(fq, 0).  The
+ * same kernels with the same parameters, and the same refusals. */
+int mosrx_launch_fwd_queue_build(const mosrx_fqparams *fq, void *stream);
+int mosrx_launch_fwd_desc_queue_build(const mosrx_fqparams *fq, const mosrx_dqparams *dq, void *stream);
+
 /* The one-launch form (mosrx_set_fwd_one): the plan and the descriptor rings of
  * every batch by one workgroup per batch, the same bytes as the four launches
  * above (no scratch is read or written).  The batches are the queue form's two

@@ -839,28 +839,69 @@ extern "C" int mosrx_launch_fwd_rings(const mosrx_rparams *rp, void *stream)
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
+// What every queue launch asks of fq, and what a ring build asks on top (host code only).
+static int fwd_queue_ok(const mosrx_fqparams *fq)
+{
+	return fq && fq->desc && fq->tab && fq->nb != 0 && (fq->rec_bytes == 8u || fq->rec_bytes == 16u);
+}
+
+static int fwd_queue_build_ok(const mosrx_fqparams *fq)
+{
+	return fq->scratch && !((uintptr_t)fq->scratch & 15) && fq->nrings >= 1u && fq->nrings <= FWD_NQ;
+}
+
+static int fwd_desc_queue_ok(const mosrx_fqparams *fq, const mosrx_dqparams *dq)
+{
+	return fwd_queue_ok(fq) && fwd_queue_build_ok(fq) && dq && dq->desc && dq->tab == fq->tab &&
+	       dq->scratch == fq->scratch && dq->nb == fq->nb && dq->total_tiles == fq->total_tiles &&
+	       dq->nrings == fq->nrings;
+}
+
+static void fwd_queue_plan_launch(const mosrx_fqparams *fq, hipStream_t s)
+{
+	const dim3 grid(fq->total_tiles), block(MOSRX_FWD_THREADS);
+	if (!fq->total_tiles)
+		return;
+	if (fq->rec_bytes == 8u)
+		hipLaunchKernelGGL(mosrx_fwd_plan_queue_kernel<8u>, grid, block, 0, s, *fq);
+	else
+		hipLaunchKernelGGL(mosrx_fwd_plan_queue_kernel<16u>, grid, block, 0, s, *fq);
+}
+
+// totals, scan (one workgroup per batch), then the byte-ring copy (dq NULL) or the descriptor store
+static void fwd_queue_build_launches(const mosrx_fqparams *fq, const mosrx_dqparams *dq, hipStream_t s)
+{
+	const dim3 grid(fq->total_tiles), block(MOSRX_FWD_THREADS);
+	if (fq->total_tiles)
+		hipLaunchKernelGGL(mosrx_fwd_ring_totals_queue_kernel, grid, block, 0, s, *fq);
+	hipLaunchKernelGGL(mosrx_fwd_ring_scan_queue_kernel, dim3(fq->nb), dim3(FWD_SCAN_THREADS), 0, s, *fq);
+	if (!fq->total_tiles)
+		return;
+	if (dq)
+		hipLaunchKernelGGL(mosrx_fwd_desc_store_queue_kernel, grid, block, 0, s, *dq);
+	else
+		hipLaunchKernelGGL(mosrx_fwd_ring_copy_queue_kernel, grid, block, 0, s, *fq);
+}
+
 extern "C" int mosrx_launch_fwd_queue(const mosrx_fqparams *fq, int with_build, void *stream)
 {
 	const hipStream_t s = (hipStream_t)stream;
-	if (!fq || !fq->desc || !fq->tab || fq->nb == 0 || (fq->rec_bytes != 8u && fq->rec_bytes != 16u))
+	if (!fwd_queue_ok(fq))
 		return -EINVAL;
-	if (with_build && (!fq->scratch || ((uintptr_t)fq->scratch & 15) || fq->nrings < 1u || fq->nrings > FWD_NQ ||
-	                   (uint64_t)fq->nrings * fq->cap_units > (1ull << 28)))
+	if (with_build && (!fwd_queue_build_ok(fq) || (uint64_t)fq->nrings * fq->cap_units > (1ull << 28)))
 		return -EINVAL;
-	const dim3 grid(fq->total_tiles), block(MOSRX_FWD_THREADS);
-	if (fq->total_tiles) {
-		if (fq->rec_bytes == 8u)
-			hipLaunchKernelGGL(mosrx_fwd_plan_queue_kernel<8u>, grid, block, 0, s, *fq);
-		else
-			hipLaunchKernelGGL(mosrx_fwd_plan_queue_kernel<16u>, grid, block, 0, s, *fq);
-	}
-	if (with_build) {
-		if (fq->total_tiles)
-			hipLaunchKernelGGL(mosrx_fwd_ring_totals_queue_kernel, grid, block, 0, s, *fq);
-		hipLaunchKernelGGL(mosrx_fwd_ring_scan_queue_kernel, dim3(fq->nb), dim3(FWD_SCAN_THREADS), 0, s, *fq);
-		if (fq->total_tiles)
-			hipLaunchKernelGGL(mosrx_fwd_ring_copy_queue_kernel, grid, block, 0, s, *fq);
-	}
+	fwd_queue_plan_launch(fq, s);
+	if (with_build)
+		fwd_queue_build_launches(fq, NULL, s);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+extern "C" int mosrx_launch_fwd_queue_build(const mosrx_fqparams *fq, void *stream)
+{
+	const hipStream_t s = (hipStream_t)stream;
+	if (!fwd_queue_ok(fq) || !fwd_queue_build_ok(fq) || (uint64_t)fq->nrings * fq->cap_units > (1ull << 28))
+		return -EINVAL;
+	fwd_queue_build_launches(fq, NULL, s);
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
@@ -898,22 +939,19 @@ extern "C" int mosrx_launch_fwd_desc(const mosrx_dparams *dp, void *stream)
 extern "C" int mosrx_launch_fwd_desc_queue(const mosrx_fqparams *fq, const mosrx_dqparams *dq, void *stream)
 {
 	const hipStream_t s = (hipStream_t)stream;
-	if (!fq || !fq->desc || !fq->tab || fq->nb == 0 || (fq->rec_bytes != 8u && fq->rec_bytes != 16u) || !fq->scratch ||
-	    ((uintptr_t)fq->scratch & 15) || fq->nrings < 1u || fq->nrings > FWD_NQ || !dq || !dq->desc ||
-	    dq->tab != fq->tab || dq->scratch != fq->scratch || dq->nb != fq->nb || dq->total_tiles != fq->total_tiles ||
-	    dq->nrings != fq->nrings)
+	if (!fwd_desc_queue_ok(fq, dq))
 		return -EINVAL;
-	const dim3 grid(fq->total_tiles), block(MOSRX_FWD_THREADS);
-	if (fq->total_tiles) {
-		if (fq->rec_bytes == 8u)
-			hipLaunchKernelGGL(mosrx_fwd_plan_queue_kernel<8u>, grid, block, 0, s, *fq);
-		else
-			hipLaunchKernelGGL(mosrx_fwd_plan_queue_kernel<16u>, grid, block, 0, s, *fq);
-		hipLaunchKernelGGL(mosrx_fwd_ring_totals_queue_kernel, grid, block, 0, s, *fq);
-	}
-	hipLaunchKernelGGL(mosrx_fwd_ring_scan_queue_kernel, dim3(fq->nb), dim3(FWD_SCAN_THREADS), 0, s, *fq);
-	if (fq->total_tiles)
-		hipLaunchKernelGGL(mosrx_fwd_desc_store_queue_kernel, grid, block, 0, s, *dq);
+	fwd_queue_plan_launch(fq, s);
+	fwd_queue_build_launches(fq, dq, s);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+extern "C" int mosrx_launch_fwd_desc_queue_build(const mosrx_fqparams *fq, const mosrx_dqparams *dq, void *stream)
+{
+	const hipStream_t s = (hipStream_t)stream;
+	if (!fwd_desc_queue_ok(fq, dq))
+		return -EINVAL;
+	fwd_queue_build_launches(fq, dq, s);
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 

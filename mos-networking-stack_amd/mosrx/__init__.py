@@ -216,6 +216,61 @@ def fwd_tables(routes=(), arp=(), netdevs=(), nic_fwd=None) -> FwdTables:
     return t
 
 
+# ---- firewall rules on SYN frames (include/mosrx.h: mosrx_acl_rule) ----
+OP_ACL = 14            # MOSRX_OP_ACL: the firewall launch (arg = rec_bytes; aux = the u16 hit arrays)
+ACL_MAX_RULES = 1024   # MOSRX_ACL_MAX_RULES (the sample's MAX_RULES)
+ACL_ACCEPT, ACL_DROP = 1, 2                       # MOSRX_ACL_*: FRA_ACCEPT, FRA_DROP
+ACL_NOT_LOOKED_UP, ACL_NO_MATCH = 0xFFFF, 0xFFFE  # d_hit values that are no rule index
+FWD_DROP = 6           # MOSRX_FWD_DROP: the plan kind of a SYN a DROP rule matched
+ACL_RULE_DTYPE = np.dtype([("src_ip", "<u4"), ("src_mask", "<u4"), ("dst_ip", "<u4"), ("dst_mask", "<u4"),
+                           ("sport", "<u2"), ("dport", "<u2"), ("action", "u1"), ("pad", "u1", 3)])
+assert ACL_RULE_DTYPE.itemsize == 24
+
+
+class AclRule(C.Structure):
+    """mosrx_acl_rule: one rule as struct FirewallRule holds it after ParseConfigFile."""
+    _fields_ = [("src_ip", C.c_uint32), ("src_mask", C.c_uint32), ("dst_ip", C.c_uint32), ("dst_mask", C.c_uint32),
+                ("sport", C.c_uint16), ("dport", C.c_uint16), ("action", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+def acl_mask(bits: int) -> int:
+    """What IP_NETMASK (simple_firewall.c:39) ands the stored, network-order address
+    with: 0xFFFFFFFF >> (32 - bits).  For bits that are no multiple of 8 this keeps
+    the LOW bits of the last partial octet -- the sample's behaviour, reproduced.
+    /0 is a shift by 32 there (undefined) and is refused: 0.0.0.0 is the wildcard."""
+    if not 1 <= bits <= 32:
+        raise ValueError(f"/{bits}: a prefix of 1..32 (0.0.0.0 is the wildcard; /0 is undefined in the sample)")
+    return 0xFFFFFFFF >> (32 - bits)
+
+
+def _acl_addr(cidr: str) -> tuple[int, int]:
+    a, _, p = cidr.partition("/")
+    m = acl_mask(int(p) if p else 32)
+    return ip_raw(a) & m, m                # ExtractIPAddress (:204) stores the masked address
+
+
+def acl_rules(rules) -> np.ndarray:
+    """The rules of a simple_firewall rule file as ACL_RULE_DTYPE records:
+    [("DROP" | "ACCEPT", "10.1.0.0/16", "10.2.0.1", sport, dport), ...], ports in
+    host order, 0 (or omitted) the wildcard, as is the address 0.0.0.0."""
+    if len(rules) > ACL_MAX_RULES:
+        raise ValueError(f"{len(rules)} rules: at most {ACL_MAX_RULES}")
+    out = np.zeros(len(rules), ACL_RULE_DTYPE)
+    for i, r in enumerate(rules):
+        act, src, dst = r[0], r[1], r[2]
+        sport, dport = (tuple(r[3:]) + (0, 0))[:2]
+        if act not in ("ACCEPT", "DROP"):
+            raise ValueError(f"rule {i}: action {act!r}")
+        if not (0 <= int(sport) <= 0xFFFF and 0 <= int(dport) <= 0xFFFF):
+            raise ValueError(f"rule {i}: port out of range")
+        out[i]["src_ip"], out[i]["src_mask"] = _acl_addr(src)
+        out[i]["dst_ip"], out[i]["dst_mask"] = _acl_addr(dst)
+        out[i]["sport"] = int.from_bytes(int(sport).to_bytes(2, "big"), "little")   # htons
+        out[i]["dport"] = int.from_bytes(int(dport).to_bytes(2, "big"), "little")
+        out[i]["action"] = ACL_ACCEPT if act == "ACCEPT" else ACL_DROP
+    return out
+
+
 class BpfProg(C.Structure):
     _fields_ = [("insns", C.c_void_p), ("len", C.c_uint32), ("len_mode", C.c_int32)]
 
@@ -509,6 +564,13 @@ def lib():
             "mosrx_slot_fwd": (I, [P, I, C.POINTER(SlotFwdOut)]),
             "mosrx_gpu_module_set_fwd": (I, [C.POINTER(FwdTables), I]),
             "mosrx_backend_forward": (I, [P, P, I, P]),
+            "mosrx_acl_check": (I, [P, U32]),
+            "mosrx_acl_set": (I, [P, P, U32]),
+            "mosrx_acl_count": (U32, [P]),
+            "mosrx_acl_apply_dev": (I, [P, C.POINTER(Batch), P, I, P, P, P, P]),
+            "mosrx_queue_set_acl": (I, [P, P, C.POINTER(P), P]),
+            "mosrx_slot_acl": (I, [P, I, C.POINTER(P), P]),
+            "mosrx_gpu_module_set_acl": (I, [P, U32]),
             "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
             "mosrx_hub_endpoint": (P, [P, U32]),
             "mosrx_hub_stats_get": (I, [P, P]),
@@ -1055,6 +1117,36 @@ class Context:
         if sync:
             _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
 
+    # ---- firewall rules ----
+    def acl_set(self, rules) -> None:
+        """mosrx_acl_set: install the firewall rules (ACL_RULE_DTYPE records, or the
+        tuples acl_rules takes); None or an empty list clears them."""
+        if rules is None or len(rules) == 0:
+            _chk(lib().mosrx_acl_set(self.handle, None, 0), "mosrx_acl_set")
+            return
+        r = rules if isinstance(rules, np.ndarray) else acl_rules(rules)
+        r = np.ascontiguousarray(r, ACL_RULE_DTYPE)
+        _chk(lib().mosrx_acl_set(self.handle, r.ctypes.data, len(r)), "mosrx_acl_set")
+
+    def acl_count(self) -> int:
+        return int(lib().mosrx_acl_count(self.handle))
+
+    def acl_apply_dev(self, b: Batch, d_rec: int, rec_bytes: int, d_plan: int | None, d_hit: int,
+                      d_counts: int | None = None, sync: bool = True, stream: int | None = None) -> None:
+        """mosrx_acl_apply_dev: the installed rules over a device-resident batch's SYN
+        frames -- a u16 hit per frame, counts added per rule, DROP rules' frames
+        taken out of the plan (device pointers; the caller owns all)."""
+        _chk(lib().mosrx_acl_apply_dev(self.handle, C.byref(b), d_rec, rec_bytes, d_plan, d_hit, d_counts, stream),
+             "mosrx_acl_apply_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
+    def slot_acl(self, slot: int, hit: list | None, counts: int | None = None) -> None:
+        """mosrx_slot_acl: arm the slot's next group submit with the firewall launch (host
+        pointers: a u16 hit array per batch, one counts array or None); hit None disarms."""
+        self._acl_arm = (C.c_void_p * len(hit))(*hit) if hit is not None else None   # must outlive the submit
+        _chk(lib().mosrx_slot_acl(self.handle, slot, self._acl_arm, counts), "mosrx_slot_acl")
+
     def slot_fwd(self, slot: int, tx_src: list | None, tx_len: list | None = None, tx_mac: list | None = None,
                  rings: list | None = None, nrings: int = 0, in_ifidx: list | None = None,
                  plan: list | None = None) -> None:
@@ -1379,6 +1471,13 @@ class Queue:
                          *[C.cast(a, C.c_void_p) for a in keep[1:]])
         _chk(lib().mosrx_queue_set_fwd_desc(self.ctx.handle, self.handle, C.byref(f)), "mosrx_queue_set_fwd_desc")
 
+    def set_acl(self, hit: list | None, counts: int | None = None) -> None:
+        """mosrx_queue_set_acl: attach the firewall launch to every run -- per-batch
+        device pointers for the u16 hit arrays, one counts array for the queue (or
+        None); between the plan and the build when forwarding is attached.  hit None detaches."""
+        h = (C.c_void_p * len(hit))(*hit) if hit is not None else None
+        _chk(lib().mosrx_queue_set_acl(self.ctx.handle, self.handle, h, counts), "mosrx_queue_set_acl")
+
     def run(self, sync: bool = True):
         _chk(lib().mosrx_queue_run(self.ctx.handle, self.handle, None), "mosrx_queue_run")
         if sync:
@@ -1447,6 +1546,12 @@ PKT_RX_STEER = 0x19
 PKT_RX_QUEUE = 0x1A
 PKT_RX_QUEUE_SIDE = 0x1B
 PKT_RX_FWD = 0x1C
+PKT_RX_ACL = 0x1D
+
+
+class AclView(C.Structure):
+    """mosrx_acl_view: dev_ioctl(MOSRX_PKT_RX_ACL)'s answer for the exposed batch."""
+    _fields_ = [("n", C.c_uint32), ("nrules", C.c_uint32), ("hit", C.c_void_p), ("counts", C.c_void_p)]
 
 
 class FwdView(C.Structure):
@@ -1487,7 +1592,8 @@ class GpuBackend:
                  timing: bool = False, flowhash: bool = False, tx_csum: bool = False, compact: bool = False,
                  group_bytes: int = 0, group_max_us: int = 0, direct_kb: int | None = None,
                  direct_frames: int | None = None, module_lib=None, steer: bool | int = False,
-                 steer_one: int = 0, fwd: FwdTables | None = None, fwd_listener: bool = False, fwd_one: int = 0):
+                 steer_one: int = 0, fwd: FwdTables | None = None, fwd_listener: bool = False, fwd_one: int = 0,
+                 acl=None):
         self.L = L = module_lib or lib()
         cfg = ModuleCfg()
         L.mosrx_gpu_module_cfg_default(C.byref(cfg))
@@ -1528,6 +1634,13 @@ class GpuBackend:
         L.mosrx_gpu_module_set_fwd.argtypes = [C.POINTER(FwdTables), C.c_int]
         _chk(L.mosrx_gpu_module_set_fwd(C.byref(fwd) if fwd is not None else None, int(bool(fwd_listener))),
              "mosrx_gpu_module_set_fwd")
+        # firewall rules (ACL_RULE_DTYPE records or acl_rules' tuples): every group submit is armed with them
+        L.mosrx_gpu_module_set_acl.restype = C.c_int
+        L.mosrx_gpu_module_set_acl.argtypes = [C.c_void_p, C.c_uint32]
+        r = None if acl is None or len(acl) == 0 else np.ascontiguousarray(
+            acl if isinstance(acl, np.ndarray) else acl_rules(acl), ACL_RULE_DTYPE)
+        _chk(L.mosrx_gpu_module_set_acl(r.ctypes.data if r is not None else None, len(r) if r is not None else 0),
+             "mosrx_gpu_module_set_acl")
         self.nif = len(sources)
         self.sources = list(sources)
         self.m = IoModuleFunc.in_dll(L, "gpu_module_func")
@@ -1625,6 +1738,17 @@ class GpuBackend:
         if self._ioctl(self.ctx, ifidx, PKT_RX_QUEUE_SIDE, C.byref(v)):
             return None
         return _queue_side_arrays(v)
+
+    def acl_view(self, ifidx: int):
+        """dev_ioctl(MOSRX_PKT_RX_ACL): the exposed batch's (hit[n], counts[nrules] so far), or
+        None when the ioctl answers -1 (no rules, no batch, the batch was touched)."""
+        v = AclView()
+        if self._ioctl(self.ctx, ifidx, PKT_RX_ACL, C.byref(v)):
+            return None
+        hit = np.ctypeslib.as_array(C.cast(v.hit, C.POINTER(C.c_uint16)), (v.n,)).copy() if v.n else np.zeros(0, np.uint16)
+        cnt = np.ctypeslib.as_array(C.cast(v.counts, C.POINTER(C.c_uint32)), (ACL_MAX_RULES,)).copy()
+        assert not cnt[v.nrules:].any()
+        return hit, cnt[:v.nrules]
 
     def fwd_view(self, ifidx: int):
         """dev_ioctl(MOSRX_PKT_RX_FWD): the exposed batch's (plan[n], tx_src[m], tx_len[m],
