@@ -758,6 +758,138 @@ int  mosrx_queue_set_acl(mosrx_ctx *c, mosrx_queue *q, uint16_t *const *d_hit, u
  * slot whatever becomes of it. */
 int  mosrx_slot_acl(mosrx_ctx *c, int slot, uint16_t *const *h_hit, uint32_t *h_counts);
 
+/* ---- NAT: established flows translated ahead of forwarding --------------------- */
+/* What samples/nat does to the TCP frames of a monitored flow (translate_addr,
+ * nat.c:91-155): the source address and port become the NAT's (client side), or
+ * the destination address and port the client's (server side), and
+ * mtcp_setlastpkt recomputes both checksums (mos_api.c:1045-1054, :1107-1122,
+ * :1179-1194); ForwardIPPacket then routes the translated daddr (ip_out.c:56-65)
+ * and copies the translated packet.  The serial part -- assign_port at a flow's
+ * first frame, release_port at its end -- stays on the host, which hands the GPU
+ * the bindings in force; the per-frame part is one launch in place of the plan
+ * launch (mosrx_fwd_plan_nat_dev) and one behind the byte-ring build
+ * (mosrx_nat_patch_rings_dev).
+ *
+ * The boundary: which frames raise MOS_ON_PKT_IN, and which side a frame is on,
+ * is the stream engine's decision behind tcp.c:445.  Here the explicit bindings
+ * decide: a frame whose 4-tuple is a binding's client-side key is SNAT, one whose
+ * 4-tuple is its server-side key is DNAT, any other eligible frame is a MISS. */
+#define MOSRX_NAT_MAX_BINDINGS 64510u   /* the sample's port pool, 1025 .. 65534 (nat.c:244) */
+/* One established flow, every field network order as the frame stores it (the
+ * raw value of a little-endian host's load). */
+typedef struct mosrx_nat_binding {
+	uint32_t cli_ip, svr_ip, nat_ip;
+	uint16_t cli_port, svr_port, nat_port;
+	uint16_t pad;
+} mosrx_nat_binding;
+enum {
+	MOSRX_NAT_NONE = 0,   /* not eligible (non-TCP, ARP, a bad checksum ...): the sample never sees it, mOS forwards it as received */
+	MOSRX_NAT_SNAT = 1,   /* client side: saddr / source := addr / port */
+	MOSRX_NAT_DNAT = 2,   /* server side: daddr / dest := addr / port */
+	MOSRX_NAT_MISS = 3,   /* eligible, no binding: the flow's first frame, for the host to assign a port */
+	MOSRX_NAT_HOST = 4    /* eligible, but doff < 5 or a segment under 20 bytes: mtcp_setlastpkt refuses the
+	                       * port write (the sample then drops the frame) or writes the check outside the segment */
+};
+#define MOSRX_NAT_NO_BIND 0xFFFFFFFFu
+/* The translation of one frame, 16 bytes.  NONE: all zero.  MISS / HOST: kind,
+ * ihl, bind = MOSRX_NAT_NO_BIND, the rest zero. */
+typedef struct mosrx_nat_xlat {
+	uint32_t addr;        /* the new saddr (SNAT) or daddr (DNAT) */
+	uint16_t port;        /* the new source (SNAT) or dest (DNAT) */
+	uint16_t ip_check;    /* iph->check after the rewrite */
+	uint16_t tcp_check;   /* tcph->check after the rewrite */
+	uint8_t  kind;        /* MOSRX_NAT_* */
+	uint8_t  ihl;         /* the frame's ihl (5 .. 15) when eligible */
+	uint32_t bind;        /* SNAT / DNAT: the binding's index in the installed array */
+} mosrx_nat_xlat;
+/* The plan kinds of the frames the launch hands to the host: both with tx_len 0,
+ * out_ifidx -1, arp_idx 0xFFFF, reserved 0.  Every build sends kinds IP and ETH
+ * only, so both fall out of all of them. */
+#define MOSRX_FWD_NAT_MISS 7
+#define MOSRX_FWD_NAT_HOST 8
+
+/* The lookup table: open addressing, linear probing, a power-of-two number of
+ * 32-byte slots, at least 4 per binding (two keys a binding: at most half full).
+ * Each binding gives two keys (saddr, daddr, ports = sport | dport << 16):
+ *   client side  (cli_ip, svr_ip, cli_port, svr_port) -> SNAT {nat_ip, nat_port}
+ *   server side  (svr_ip, nat_ip, svr_port, nat_port) -> DNAT {cli_ip, cli_port}
+ * A key lives at slot (mosrx_nat_hash(key) + d) & (slots - 1) for the least d
+ * whose slot was free when it went in; kind 0 marks a free slot.  No GPU needed
+ * for any of these four. */
+typedef struct mosrx_nat_slot {
+	uint32_t saddr, daddr, ports;
+	uint16_t port;        /* the value: new port, */
+	uint8_t  kind;        /*   MOSRX_NAT_SNAT or MOSRX_NAT_DNAT (0: free), */
+	uint8_t  pad;
+	uint32_t addr;        /*   new address */
+	uint32_t bind;        /*   and the binding's index */
+	uint32_t reserved[2];
+} mosrx_nat_slot;
+uint32_t mosrx_nat_hash(uint32_t saddr, uint32_t daddr, uint32_t ports);
+/* Slots of the table of n bindings: a power of two, >= 16 and >= 4 * n. */
+uint32_t mosrx_nat_slots(uint32_t n);
+/* Build the table of n bindings into slots[mosrx_nat_slots(n)] (overwritten
+ * whole); *probe (may be NULL): the most slots any key's lookup examines, 0 for
+ * n == 0 -- the kernel's loop bound.  -EINVAL as mosrx_nat_check. */
+int  mosrx_nat_build(const mosrx_nat_binding *b, uint32_t n, mosrx_nat_slot *slots, uint32_t *probe);
+/* 0, or -EINVAL for n over MOSRX_NAT_MAX_BINDINGS, b NULL with n != 0, a zero
+ * nat_ip or nat_port, or two keys that are equal -- two client-side keys, two
+ * server-side keys, or one of each: a frame must find one answer.  (-ENOMEM:
+ * the check builds the table.) */
+int  mosrx_nat_check(const mosrx_nat_binding *b, uint32_t n);
+/* Validate and build the table on the host and upload it; in effect for
+ * launches submitted after it returns.  The device copies rotate over a pool
+ * under mosrx_fwd_set's discipline: one a launch may read is rewritten only
+ * after that launch drained.  NULL / 0 clears the table, which still counts as
+ * set: every eligible frame is then a MISS. */
+int  mosrx_nat_set(mosrx_ctx *c, const mosrx_nat_binding *b, uint32_t n);
+/* Bindings installed. */
+uint32_t mosrx_nat_count(const mosrx_ctx *c);
+
+/* One launch in place of mosrx_fwd_plan_dev (same arguments, same plan for every
+ * frame that is not translated).  A frame is eligible when its reason is TCP_OK,
+ * num_msp != 0, the listener flag is off and its IPv4 packet lies inside the
+ * capture (the plan's ip_ok).  Its key is read from the frame as the firewall
+ * launch reads it (past-the-end bytes read zero) and looked up; d_xlat[i] (16-byte
+ * aligned) is written for every frame.  A DNAT frame is routed and ARP-resolved
+ * on the translated daddr.  ip_check is ip_fast_csum over the translated header;
+ * tcp_check follows from the received check word alone (TCP_OK: the received
+ * segment sums to 0xFFFF), TCPCalcChecksum's value bit for bit.  Under forward
+ * != 0 a MISS / HOST frame's plan record is the MOSRX_FWD_NAT_* record above.
+ * The returns in their order: -EINVAL for a NULL or misaligned pointer (d_xlat
+ * to 16, d_plan to 8), a bad rec_bytes or in_ifidx, or a context under
+ * skip_tcp_csum (the segment was never summed: no exact incremental check);
+ * -ENOENT without forwarding tables, then without mosrx_nat_set; n == 0: 0,
+ * nothing launched.  Allocates nothing, graph-capturable. */
+int  mosrx_fwd_plan_nat_dev(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec, int rec_bytes, int in_ifidx,
+                            mosrx_fwd *d_plan, mosrx_nat_xlat *d_xlat, void *stream);
+/* One launch behind mosrx_fwd_build_rings_dev on the same stream, over its
+ * outputs: entry e of a ring's written frames (start <= e < start + count;
+ * dropped and unwritten entries are never read) whose frame i = d_tx_src[e] is
+ * SNAT / DNAT gets, at d_tx_off[e] in d_tx_frames: ip_check at byte 24, addr at
+ * 26 (SNAT) or 30 (DNAT), port at 14 + 4 * ihl (SNAT) or two bytes on (DNAT),
+ * tcp_check at 14 + 4 * ihl + 16.  n: the batch's frames (the entry arrays' and
+ * d_xlat's length).  -EINVAL: NULL or misaligned pointer (d_xlat, d_tx_frames,
+ * d_rings to 16, d_tx_off / d_tx_src to 4), nrings outside
+ * 1 .. MOSRX_FWD_MAX_NETDEVS.  n == 0 launches nothing.  The descriptor form
+ * needs no such launch: there d_xlat[d_tx_src[e]] is the host's descriptor. */
+int  mosrx_nat_patch_rings_dev(mosrx_ctx *c, const mosrx_nat_xlat *d_xlat, uint8_t *d_tx_frames,
+                               const uint32_t *d_tx_off, const uint32_t *d_tx_src, const mosrx_fwd_ring *d_rings,
+                               uint32_t nrings, uint32_t n, void *stream);
+/* One record applied to one host frame (from its Ethernet header; NONE / MISS /
+ * HOST: untouched): the definition the launch above is tested against. */
+void mosrx_nat_patch_frame(uint8_t *frame, const mosrx_nat_xlat *x);
+/* The batch-queue form: d_xlat[nb], one array per batch (of an empty batch it may
+ * be NULL).  With mosrx_queue_set_fwd attached a run issues classify, (steer,)
+ * plan-nat, the build's three launches and the patch; with
+ * mosrx_queue_set_fwd_desc plan-nat and the descriptor build's three; each one
+ * launch over all batches.  Such a queue takes the multi-launch path whatever
+ * mosrx_set_fwd_one says.  -EINVAL with no forwarding attached or with firewall
+ * rules attached (here, and again at the run should the attachments have changed),
+ * and for a misaligned array.  A run is refused before it enqueues anything with
+ * -ENOENT (no bindings set) or -EINVAL (skip_tcp_csum).  NULL detaches. */
+int  mosrx_queue_set_nat(mosrx_ctx *c, mosrx_queue *q, mosrx_nat_xlat *const *d_xlat);
+
 /* End-to-end: host frames -> pinned staging -> H2D -> kernel -> D2H -> h_out.
  * Blocks until h_out is filled.  When frames, off and len lie in ONE host
  * block (any order, not overlapping frames_bytes, frames 16-byte aligned
@@ -934,7 +1066,11 @@ enum { MOSRX_OP_CLASSIFY = 0, MOSRX_OP_CLASSIFY_FH = 1, MOSRX_OP_BPF = 2, MOSRX_
                                * tables' num_netdevs */,
        MOSRX_OP_ACL = 14 /* the firewall launch (mosrx_acl_apply_dev) over records already made: out[i] the records
                           * of batch i, aux[i] its u16 hit array, `arg` = rec_bytes; no plan and no counts.  Not a
-                          * kernel of the classify object: -ENOTSUP from mosrx_time_op_dispatch */ };
+                          * kernel of the classify object: -ENOTSUP from mosrx_time_op_dispatch */,
+       MOSRX_OP_FWD_NAT = 15 /* plan-nat, the ring build and the patch (mosrx_fwd_plan_nat_dev,
+                              * mosrx_fwd_build_rings_dev, mosrx_nat_patch_rings_dev) over records already made:
+                              * out / aux / `arg` as MOSRX_OP_FWD_RINGS; the xlat array is the timing call's own.
+                              * -ENOTSUP from mosrx_time_op_dispatch */ };
 int  mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t nb, void *const *out,
                    void *const *aux, uint32_t iters, uint32_t nstreams, float *total_ms, float *avg_kernel_ms);
 /* The kernel's own duration, averaged over `iters` back-to-back launches on

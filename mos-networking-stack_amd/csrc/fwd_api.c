@@ -136,6 +136,8 @@ static void fwd_mark_used(mosrx_ctx *c)
 	c->fwd_pool_used[(c->fwd_pool_next + MOSRX_FWD_POOL - 1) % MOSRX_FWD_POOL] = 1;
 }
 
+void mosrx__fwd_mark_used(mosrx_ctx *c) { fwd_mark_used(c); }
+
 /* What a planning launch takes from the context: the installed tables and
  * mosrx_mos_forwards' parameters, into the fields of mosrx_fparams,
  * mosrx_fqparams or mosrx_oparams that carry them. */
@@ -893,7 +895,9 @@ int mosrx__fwd_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, 
  * batch sent whole (its frame bytes + 32 a frame; the rings together at most
  * 4 GiB), tx_off, tx_src, tx_len, tx_nif, tx_count / the ring rows, scratch.
  * MOSRX_OP_FWD_DESC takes the same block: its tx_mac (12 bytes an entry) lies
- * where the rings would (each has room for 32 bytes a frame). */
+ * where the rings would (each has room for 32 bytes a frame).  MOSRX_OP_FWD_NAT
+ * takes MOSRX_OP_FWD_RINGS' block with its xlat array (16 bytes a frame) behind
+ * the scratch. */
 int mosrx__fwd_tmp_reserve(mosrx_ctx *c, int op, const mosrx_batch *b, uint32_t nb)
 {
 	const uint32_t nrings = op == MOSRX_OP_FWD || !c->fwd_num_netdevs ? 1 : c->fwd_num_netdevs;
@@ -915,7 +919,8 @@ int mosrx__fwd_tmp_reserve(mosrx_ctx *c, int op, const mosrx_batch *b, uint32_t 
 	c->fwd_tmp_cap = cap;
 	c->fwd_tmp_rings = nrings;
 	stride = c->fwd_tmp_cap * nrings + 2 * TMP_RND((size_t)maxn * 4) + TMP_RND((size_t)maxn * 2) + TMP_RND(maxn) + 256 +
-	         TMP_RND(mosrx_fwd_rings_scratch_bytes(maxn, nrings));
+	         TMP_RND(mosrx_fwd_rings_scratch_bytes(maxn, nrings)) +
+	         (op == MOSRX_OP_FWD_NAT ? TMP_RND((size_t)maxn * sizeof(mosrx_nat_xlat)) : 0);
 	bytes = stride * (MOSRX_MAX_STREAMS + 1);
 	if (bytes > c->fwd_tmp_bytes) {
 		HIPCHK(hipDeviceSynchronize());
@@ -938,7 +943,7 @@ int mosrx__fwd_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 	const size_t w = TMP_RND((size_t)c->fwd_tmp_n * 4);
 	/* the descriptor form under mosrx_set_fwd_one's limit: plan and rings in one launch, below */
 	const int one = op == MOSRX_OP_FWD_DESC && c->fwd_one && b->n <= c->fwd_one;
-	int rc = one ? 0 : mosrx_fwd_plan_dev(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, s);
+	int rc = one || op == MOSRX_OP_FWD_NAT ? 0 : mosrx_fwd_plan_dev(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, s);
 	if (rc || op == MOSRX_OP_FWD_PLAN)
 		return rc;
 	/* the stream's own block: launches on different streams overlap */
@@ -959,6 +964,17 @@ int mosrx__fwd_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 		return mosrx_fwd_desc_rings_dev(c, b, (const mosrx_fwd *)aux, c->fwd_tmp_rings, (uint32_t *)tsrc, (uint16_t *)tlen,
 		                                (uint32_t *)blk, (mosrx_fwd_ring *)tcnt, scr,
 		                                TMP_RND(mosrx_fwd_desc_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)), s);
+	if (op == MOSRX_OP_FWD_NAT) {
+		/* plan-nat in the plan's place, the ring build, the patch; the xlat array behind the scratch */
+		mosrx_nat_xlat *xl = (mosrx_nat_xlat *)(scr + TMP_RND(mosrx_fwd_rings_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)));
+		if ((rc = mosrx_fwd_plan_nat_dev(c, b, out, arg & 0xFF, arg >> 8, (mosrx_fwd *)aux, xl, s)) ||
+		    (rc = mosrx_fwd_build_rings_dev(c, b, (const mosrx_fwd *)aux, blk, c->fwd_tmp_cap, c->fwd_tmp_rings,
+		                                    (uint32_t *)toff, (uint16_t *)tlen, (uint32_t *)tsrc, (mosrx_fwd_ring *)tcnt, scr,
+		                                    TMP_RND(mosrx_fwd_rings_scratch_bytes(c->fwd_tmp_n, c->fwd_tmp_rings)), s)))
+			return rc;
+		return mosrx_nat_patch_rings_dev(c, xl, blk, (const uint32_t *)toff, (const uint32_t *)tsrc,
+		                                 (const mosrx_fwd_ring *)tcnt, c->fwd_tmp_rings, b->n, s);
+	}
 	if (op == MOSRX_OP_FWD_RINGS)
 		return mosrx_fwd_build_rings_dev(c, b, (const mosrx_fwd *)aux, blk, c->fwd_tmp_cap, c->fwd_tmp_rings,
 		                                 (uint32_t *)toff, (uint16_t *)tlen, (uint32_t *)tsrc, (mosrx_fwd_ring *)tcnt, scr,

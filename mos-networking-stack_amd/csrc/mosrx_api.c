@@ -330,6 +330,7 @@ void mosrx_close(mosrx_ctx *c)
 		if (c->d_fwd_pool[i])
 			hipFree(c->d_fwd_pool[i]);
 	mosrx__acl_free(c);
+	mosrx__nat_free(c);
 	for (i = 0; i < MOSRX_BPF_POOL; i++)
 		if (c->d_bpf_pool[i])
 			hipFree(c->d_bpf_pool[i]);
@@ -1908,7 +1909,8 @@ static int steer_tmp_reserve(mosrx_ctx *c, const mosrx_batch *b, uint32_t nb)
 	return 0;
 }
 
-#define OP_IS_FWD(op) ((op) == MOSRX_OP_FWD_PLAN || (op) == MOSRX_OP_FWD || (op) == MOSRX_OP_FWD_RINGS || (op) == MOSRX_OP_FWD_DESC)
+#define OP_IS_FWD(op) ((op) == MOSRX_OP_FWD_PLAN || (op) == MOSRX_OP_FWD || (op) == MOSRX_OP_FWD_RINGS || (op) == MOSRX_OP_FWD_DESC || \
+                        (op) == MOSRX_OP_FWD_NAT)
 
 /* One enqueue of operation `op` on batch b (see mosrx_time_op). */
 static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out, void *aux, hipStream_t s)
@@ -1965,7 +1967,8 @@ static int run_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, void *out
 	case MOSRX_OP_FWD_PLAN:
 	case MOSRX_OP_FWD:
 	case MOSRX_OP_FWD_RINGS:
-	case MOSRX_OP_FWD_DESC: return mosrx__fwd_op(c, op, arg, b, out, aux, s);
+	case MOSRX_OP_FWD_DESC:
+	case MOSRX_OP_FWD_NAT: return mosrx__fwd_op(c, op, arg, b, out, aux, s);
 	case MOSRX_OP_ACL: return mosrx_acl_apply_dev(c, b, out, arg, NULL, (uint16_t *)aux, NULL, s);
 	default: return -EINVAL;
 	}
@@ -2053,7 +2056,7 @@ int mosrx_time_op(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, uint32_t 
 {
 	int rc;
 	if (!c || !b || nb == 0 || iters == 0 || nstreams == 0 || nstreams > MOSRX_MAX_STREAMS ||
-	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_ACL || (op != MOSRX_OP_TX_CSUM && !out) ||
+	    op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_NAT || (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
 	      OP_IS_FWD(op) || op == MOSRX_OP_ACL) && !aux) ||
 	    (OP_IS_FWD(op) && (((arg & 0xFF) != 8 && (arg & 0xFF) != 16) || (arg >> 8) < 0 ||
@@ -2128,7 +2131,7 @@ int mosrx_time_op_dispatch(mosrx_ctx *c, int op, int arg, const mosrx_batch *b, 
                            void *const *aux, uint32_t iters, float *avg_ms)
 {
 	struct op_run r = {op, arg, b, nb, out, aux};
-	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_ACL ||
+	if (!c || !b || nb == 0 || iters == 0 || !avg_ms || op < MOSRX_OP_CLASSIFY || op > MOSRX_OP_FWD_NAT ||
 	    (op != MOSRX_OP_TX_CSUM && !out) ||
 	    ((op == MOSRX_OP_CLASSIFY_FH || op == MOSRX_OP_CLASSIFY_BPF || op == MOSRX_OP_CLASSIFY_TI || OP_IS_STEER(op) ||
 	      OP_IS_FWD(op) || op == MOSRX_OP_ACL) && !aux))
@@ -2390,10 +2393,18 @@ int mosrx_queue_run(mosrx_ctx *c, const mosrx_queue *q, void *stream)
 		return rc;
 	if (c && q && q->acl && (rc = mosrx__acl_queue_check(c, q)))
 		return rc;
+	if (c && q && q->nat && (rc = mosrx__nat_queue_check(c, q)))
+		return rc;
 	if ((rc = queue_classify(c, q, stream)))
 		return rc;
 	if (q->steer && (rc = queue_steer(c, q, stream)))
 		return rc;
+	if (q->nat) {
+		/* plan-nat in the plan launch's place, the attached build, the patch behind byte rings: never the one-launch form */
+		if ((rc = mosrx__nat_queue_launch_plan(c, q, stream)) || (rc = mosrx__fwd_queue_launch_build(c, q, stream)))
+			return rc;
+		return q->fwd_build ? mosrx__nat_queue_launch_patch(c, q, stream) : 0;
+	}
 	if (!q->acl)
 		return q->fwd ? mosrx__fwd_queue_launch(c, q, stream) : 0;
 	/* the firewall launch between the plan and the build: never the one-launch form */
@@ -2682,6 +2693,8 @@ void mosrx_queue_destroy(mosrx_ctx *c, mosrx_queue *q)
 		hipFree(q->d_ddesc);
 	if (q->d_adesc)
 		hipFree(q->d_adesc);
+	if (q->d_nxtab)
+		hipFree(q->d_nxtab);
 	free(q->h_desc);
 	free(q->d_match);
 	free(q);

@@ -1,6 +1,6 @@
 /*
  * mosrx_ctx.h — host-side context layout shared by the C host files
- * (mosrx_api.c, bpf_api.c, fwd_api.c, acl_api.c).  Not part of the ABI.
+ * (mosrx_api.c, bpf_api.c, fwd_api.c, acl_api.c, nat_api.c).  Not part of the ABI.
  */
 #ifndef MOSRX_CTX_H
 #define MOSRX_CTX_H
@@ -12,6 +12,7 @@
 #include "mosrx_steer.h"
 #include "mosrx_fwd.h"
 #include "mosrx_acl.h"
+#include "mosrx_nat.h"
 
 #define HIPCHK(x) do { if ((x) != hipSuccess) return -EIO; } while (0)
 
@@ -19,6 +20,7 @@
 #define MOSRX_BPF_POOL 8         /* device buffers the interpreter's instructions rotate over */
 #define MOSRX_FWD_POOL 4         /* device copies the forwarding tables rotate over */
 #define MOSRX_ACL_POOL 4         /* device copies the firewall rules rotate over */
+#define MOSRX_NAT_POOL 4         /* device copies the NAT lookup table rotates over */
 
 /* The fused classify + BPF kernels of a compiled set (bpf_jit.c k_fused_main):
  * one batch as the stream tile (non-temporal / cached tails) or the SMALL tile,
@@ -195,6 +197,15 @@ struct mosrx_ctx {
 	int acl_pool_used[MOSRX_ACL_POOL];
 	uint32_t acl_pool_next;
 	uint32_t acl_n;                  /* the installed rules' count */
+	/* NAT bindings (mosrx_nat_set): the installed lookup table's device copy (NULL:
+	 * never set), one of a pool under the forwarding tables' discipline; a copy
+	 * grows when a table needs more slots than it has */
+	mosrx_nat_slot *d_nat;
+	mosrx_nat_slot *d_nat_pool[MOSRX_NAT_POOL];
+	size_t nat_pool_bytes[MOSRX_NAT_POOL];
+	int nat_pool_used[MOSRX_NAT_POOL];
+	uint32_t nat_pool_next;
+	uint32_t nat_n, nat_mask, nat_probe;   /* the installed table: bindings, slots - 1, the longest probe run */
 };
 
 /* ---- batch queue (one launch over many resident batches) ---- */
@@ -244,6 +255,10 @@ struct mosrx_queue {
 	uint32_t *acl_counts;
 	uint32_t acl_tiles;
 	int acl;
+	/* NAT (mosrx_queue_set_nat): the batches' xlat arrays, a device table parallel
+	 * to d_fdesc allocated at the first attach; nat: attached */
+	mosrx_nat_xlat **d_nxtab;
+	int nat;
 };
 
 int mosrx__check_batch(const mosrx_batch *b, int dev);
@@ -362,5 +377,21 @@ int mosrx__acl_group_launch(mosrx_ctx *c, struct slot *s, const mosrx_batch *b, 
                             int with_plan, uint16_t *const *h_hit, uint32_t *h_counts);
 /* The context's device copies, at close. */
 void mosrx__acl_free(mosrx_ctx *c);
+
+/* ---- NAT's host side (nat_api.c), as mosrx_api.c's flows reach it ---- */
+
+/* A launch that reads the installed forwarding tables is about to go to stream
+ * (fwd_api.c: plan-nat reads them as the plan launch does). */
+void mosrx__fwd_mark_used(mosrx_ctx *c);
+/* A queue's conditions at run time (mosrx_queue_run asks before it enqueues
+ * anything): -EINVAL with no forwarding or with firewall rules attached, or under
+ * skip_tcp_csum; -ENOENT with no bindings set. */
+int mosrx__nat_queue_check(const mosrx_ctx *c, const mosrx_queue *q);
+/* plan-nat over the queue's batches in the plan launch's place, and the patch
+ * behind the byte-ring build; one launch each. */
+int mosrx__nat_queue_launch_plan(mosrx_ctx *c, const mosrx_queue *q, void *stream);
+int mosrx__nat_queue_launch_patch(mosrx_ctx *c, const mosrx_queue *q, void *stream);
+/* The context's device copies, at close. */
+void mosrx__nat_free(mosrx_ctx *c);
 
 #endif

@@ -8,6 +8,12 @@
 //               copies the walked tables into LDS and ends in a barrier
 //             2 record: i < p.n and part 1's names in scope; declares o (the frame's
 //               offset) and v, the two dwords of plan[i] (not stored here)
+//   FWD_PLAN_DADDR  the address part 2 routes and ARP-resolves; unless the
+//               including file defines it (the NAT plan: the translated daddr), the
+//               frame's own (rs and o are in scope where it is evaluated)
+#ifndef FWD_PLAN_DADDR
+#define FWD_PLAN_DADDR fwd_ld32(rs, o + 30u)
+#endif
 #if FWD_PLAN == 1
 	const mosrx_fwd_dev *T = p.tab;
 	const uint32_t nr = min(T->num_routes, (uint32_t)MOSRX_FWD_MAX_ROUTES);
@@ -35,7 +41,7 @@
 	const uint32_t cap = eff_caplen(o, p.len[i], p.frames_bytes);
 	const __amdgpu_buffer_rsrc_t rs = frame_rsrc(p.frames, p.frames_bytes);
 	const uint32_t w_len = fwd_ld32(rs, o + 16u);     // iph->tot_len (network order) in the low half
-	const uint32_t daddr = fwd_ld32(rs, o + 30u);     // iph->daddr as mOS loads it
+	const uint32_t daddr = FWD_PLAN_DADDR;            // iph->daddr as mOS loads it
 	const uint32_t ip_len = ((w_len & 0xFFu) << 8) | ((w_len >> 8) & 0xFFu);
 	// mosrx_mos_forwards (csrc/rx_loop.c)
 	const uint32_t bit = 1u << reason;

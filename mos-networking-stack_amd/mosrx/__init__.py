@@ -271,6 +271,60 @@ def acl_rules(rules) -> np.ndarray:
     return out
 
 
+# ---- NAT: established flows translated ahead of forwarding (include/mosrx.h) ----
+OP_FWD_NAT = 15              # MOSRX_OP_FWD_NAT: plan-nat, ring build, patch (arg / aux as OP_FWD_RINGS)
+NAT_MAX_BINDINGS = 64510     # MOSRX_NAT_MAX_BINDINGS (the sample's port pool)
+NAT_NONE, NAT_SNAT, NAT_DNAT, NAT_MISS, NAT_HOST = range(5)   # MOSRX_NAT_*
+NAT_NO_BIND = 0xFFFFFFFF
+FWD_NAT_MISS, FWD_NAT_HOST = 7, 8                              # MOSRX_FWD_NAT_*: plan kinds handed to the host
+NAT_BINDING_DTYPE = np.dtype([("cli_ip", "<u4"), ("svr_ip", "<u4"), ("nat_ip", "<u4"), ("cli_port", "<u2"),
+                              ("svr_port", "<u2"), ("nat_port", "<u2"), ("pad", "<u2")])
+NAT_XLAT_DTYPE = np.dtype([("addr", "<u4"), ("port", "<u2"), ("ip_check", "<u2"), ("tcp_check", "<u2"), ("kind", "u1"),
+                           ("ihl", "u1"), ("bind", "<u4")])
+NAT_SLOT_DTYPE = np.dtype([("saddr", "<u4"), ("daddr", "<u4"), ("ports", "<u4"), ("port", "<u2"), ("kind", "u1"),
+                           ("pad", "u1"), ("addr", "<u4"), ("bind", "<u4"), ("reserved", "<u4", 2)])
+assert NAT_BINDING_DTYPE.itemsize == 20 and NAT_XLAT_DTYPE.itemsize == 16 and NAT_SLOT_DTYPE.itemsize == 32
+
+
+def _htons(x: int) -> int:
+    return int.from_bytes(int(x).to_bytes(2, "big"), "little")
+
+
+def nat_bindings(flows, nat_ip: str) -> np.ndarray:
+    """Established flows as NAT_BINDING_DTYPE records: [(cli_ip, cli_port, svr_ip,
+    svr_port, nat_port), ...] with dotted quads and host-order ports; nat_ip the
+    NAT's own address (the sample's g_NATIP).  Stored network order, as the frame
+    holds them."""
+    if len(flows) > NAT_MAX_BINDINGS:
+        raise ValueError(f"{len(flows)} bindings: at most {NAT_MAX_BINDINGS}")
+    out = np.zeros(len(flows), NAT_BINDING_DTYPE)
+    for i, (cip, cport, sip, sport, nport) in enumerate(flows):
+        if not all(0 <= int(x) <= 0xFFFF for x in (cport, sport, nport)):
+            raise ValueError(f"binding {i}: port out of range")
+        out[i] = (ip_raw(cip), ip_raw(sip), ip_raw(nat_ip), _htons(cport), _htons(sport), _htons(nport), 0)
+    return out
+
+
+def nat_table(bindings: np.ndarray):
+    """mosrx_nat_build: (slots as NAT_SLOT_DTYPE, the longest probe run) -- the lookup
+    table mosrx_nat_set uploads, built on the host.  Raises MosrxError as mosrx_nat_check."""
+    b = np.ascontiguousarray(bindings, NAT_BINDING_DTYPE)
+    slots = np.zeros(lib().mosrx_nat_slots(len(b)), NAT_SLOT_DTYPE)
+    probe = C.c_uint32()
+    _chk(lib().mosrx_nat_build(b.ctypes.data if len(b) else None, len(b), slots.ctypes.data, C.byref(probe)),
+         "mosrx_nat_build")
+    return slots, int(probe.value)
+
+
+def nat_patch_frame(frame, xlat) -> np.ndarray:
+    """mosrx_nat_patch_frame: a copy of one host frame (from its Ethernet header) with
+    one NAT_XLAT_DTYPE record applied."""
+    f = np.array(np.frombuffer(bytes(frame), np.uint8), copy=True)
+    x = np.ascontiguousarray(np.asarray(xlat, NAT_XLAT_DTYPE).reshape(1))
+    lib().mosrx_nat_patch_frame(f.ctypes.data, x.ctypes.data)
+    return f
+
+
 class BpfProg(C.Structure):
     _fields_ = [("insns", C.c_void_p), ("len", C.c_uint32), ("len_mode", C.c_int32)]
 
@@ -571,6 +625,16 @@ def lib():
             "mosrx_queue_set_acl": (I, [P, P, C.POINTER(P), P]),
             "mosrx_slot_acl": (I, [P, I, C.POINTER(P), P]),
             "mosrx_gpu_module_set_acl": (I, [P, U32]),
+            "mosrx_nat_hash": (U32, [U32, U32, U32]),
+            "mosrx_nat_slots": (U32, [U32]),
+            "mosrx_nat_build": (I, [P, U32, P, C.POINTER(U32)]),
+            "mosrx_nat_check": (I, [P, U32]),
+            "mosrx_nat_set": (I, [P, P, U32]),
+            "mosrx_nat_count": (U32, [P]),
+            "mosrx_fwd_plan_nat_dev": (I, [P, C.POINTER(Batch), P, I, I, P, P, P]),
+            "mosrx_nat_patch_rings_dev": (I, [P, P, P, P, P, P, U32, U32, P]),
+            "mosrx_nat_patch_frame": (None, [P, P]),
+            "mosrx_queue_set_nat": (I, [P, P, C.POINTER(P)]),
             "mosrx_hub_open": (I, [P, P, I, U32, C.POINTER(P)]),
             "mosrx_hub_endpoint": (P, [P, U32]),
             "mosrx_hub_stats_get": (I, [P, P]),
@@ -1141,6 +1205,37 @@ class Context:
         if sync:
             _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
 
+    # ---- NAT ----
+    def nat_set(self, bindings) -> None:
+        """mosrx_nat_set: install the bindings (NAT_BINDING_DTYPE records); None or an
+        empty array installs the empty table (every eligible frame is then a MISS)."""
+        if bindings is None or len(bindings) == 0:
+            _chk(lib().mosrx_nat_set(self.handle, None, 0), "mosrx_nat_set")
+            return
+        b = np.ascontiguousarray(bindings, NAT_BINDING_DTYPE)
+        _chk(lib().mosrx_nat_set(self.handle, b.ctypes.data, len(b)), "mosrx_nat_set")
+
+    def nat_count(self) -> int:
+        return int(lib().mosrx_nat_count(self.handle))
+
+    def fwd_plan_nat_dev(self, b: Batch, d_rec: int, rec_bytes: int, in_ifidx: int, d_plan: int, d_xlat: int,
+                         sync: bool = True, stream: int | None = None) -> None:
+        """mosrx_fwd_plan_nat_dev: fwd_plan_dev with the installed bindings applied -- one
+        NAT_XLAT_DTYPE record per frame besides the plan (device pointers; the caller owns all)."""
+        _chk(lib().mosrx_fwd_plan_nat_dev(self.handle, C.byref(b), d_rec, rec_bytes, in_ifidx, d_plan, d_xlat, stream),
+             "mosrx_fwd_plan_nat_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
+    def nat_patch_rings_dev(self, d_xlat: int, d_tx_frames: int, d_tx_off: int, d_tx_src: int, d_rings: int,
+                            nrings: int, n: int, sync: bool = True, stream: int | None = None) -> None:
+        """mosrx_nat_patch_rings_dev: the translations stored into the frames
+        fwd_build_rings_dev built from the same plan."""
+        _chk(lib().mosrx_nat_patch_rings_dev(self.handle, d_xlat, d_tx_frames, d_tx_off, d_tx_src, d_rings, nrings, n,
+                                             stream), "mosrx_nat_patch_rings_dev")
+        if sync:
+            _chk(lib().mosrx_sync(self.handle), "mosrx_sync")
+
     def slot_acl(self, slot: int, hit: list | None, counts: int | None = None) -> None:
         """mosrx_slot_acl: arm the slot's next group submit with the firewall launch (host
         pointers: a u16 hit array per batch, one counts array or None); hit None disarms."""
@@ -1477,6 +1572,13 @@ class Queue:
         None); between the plan and the build when forwarding is attached.  hit None detaches."""
         h = (C.c_void_p * len(hit))(*hit) if hit is not None else None
         _chk(lib().mosrx_queue_set_acl(self.ctx.handle, self.handle, h, counts), "mosrx_queue_set_acl")
+
+    def set_nat(self, xlat: list | None) -> None:
+        """mosrx_queue_set_nat: plan-nat in the plan launch's place (and the patch behind
+        byte rings) on every run -- per-batch device pointers for the NAT_XLAT_DTYPE
+        arrays; needs forwarding attached and no firewall rules.  None detaches."""
+        x = (C.c_void_p * len(xlat))(*xlat) if xlat is not None else None
+        _chk(lib().mosrx_queue_set_nat(self.ctx.handle, self.handle, x), "mosrx_queue_set_nat")
 
     def run(self, sync: bool = True):
         _chk(lib().mosrx_queue_run(self.ctx.handle, self.handle, None), "mosrx_queue_run")
