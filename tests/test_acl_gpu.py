@@ -160,10 +160,10 @@ def expect_images(r, hit, cnt):
 
 
 def check(ctx, buf, off, ln, rules, rec_bytes=16, forward=1, listener=False, frames_bytes=None, rec=None, launches=1,
-          downstream=False):
+          downstream=False, tables=TABLES, nrings=2):
     """Plan + firewall launch on the GPU equal the restatement: hit, counts (after `launches`
     launches into the same array) and the amended plan, canaries included; returns (hit, plan)."""
-    t = setup(ctx, rules, forward, listener)
+    t = setup(ctx, rules, forward, listener, tables)
     orec = O.classify(buf, off, ln, O.params(num_msp=1, forward=forward)) if rec is None else rec
     base = F.plan(buf, off, ln, orec["reason"], t, 0, forward=forward, num_msp=1, listener=listener,
                   frames_bytes=frames_bytes)
@@ -184,13 +184,14 @@ def check(ctx, buf, off, ln, rules, rec_bytes=16, forward=1, listener=False, fra
         assert not len(bad), [(int(i), got[i].tolist(), want[i].tolist()) for i in bad[:6]]
         if downstream:
             # the builds omit exactly the dropped SYNs: the restatements fed the amended plan
-            dev, init = r.build_desc(2)
-            desc_same(download(dev, init), FD.build(buf, off, want, t, 2, *init), "descriptor rings")
-            cap = max(int(FR.need_units(want, 2).max()) * 16, 16)
-            dev, init = r.build_rings(cap, 2)
-            rings_same(download(dev, init), FR.build(buf, off, want, t, cap, 2, *init), "byte rings")
-            sent = FR.sent_mask(want, 2)
-            assert not sent[A.dropped(hit, rules)].any() and sent.sum() == FR.sent_mask(base, 2).sum() - A.dropped(hit, rules).sum()
+            dev, init = r.build_desc(nrings)
+            desc_same(download(dev, init), FD.build(buf, off, want, t, nrings, *init), "descriptor rings")
+            cap = max(int(FR.need_units(want, nrings).max()) * 16, 16)
+            dev, init = r.build_rings(cap, nrings)
+            rings_same(download(dev, init), FR.build(buf, off, want, t, cap, nrings, *init), "byte rings")
+            sent = FR.sent_mask(want, nrings)
+            assert not sent[A.dropped(hit, rules)].any() and \
+                sent.sum() == FR.sent_mask(base, nrings).sum() - A.dropped(hit, rules).sum()
         return hit, want
     finally:
         r.free()
