@@ -819,7 +819,7 @@ typedef struct mosrx_nat_xlat {
 typedef struct mosrx_nat_slot {
 	uint32_t saddr, daddr, ports;
 	uint16_t port;        /* the value: new port, */
-	uint8_t  kind;        /*   MOSRX_NAT_SNAT or MOSRX_NAT_DNAT (0: free), */
+	uint8_t  kind;        /*   MOSRX_NAT_SNAT or MOSRX_NAT_DNAT (0: free; MOSRX_NAT_TOMB: deleted, below), */
 	uint8_t  pad;
 	uint32_t addr;        /*   new address */
 	uint32_t bind;        /*   and the binding's index */
@@ -843,8 +843,87 @@ int  mosrx_nat_check(const mosrx_nat_binding *b, uint32_t n);
  * after that launch drained.  NULL / 0 clears the table, which still counts as
  * set: every eligible frame is then a MISS. */
 int  mosrx_nat_set(mosrx_ctx *c, const mosrx_nat_binding *b, uint32_t n);
-/* Bindings installed. */
+/* Bindings installed (live ones, after mosrx_nat_update). */
 uint32_t mosrx_nat_count(const mosrx_ctx *c);
+
+/* ---- bindings added and removed in place ---- */
+/* A slot whose key was deleted: kind MOSRX_NAT_TOMB, every other byte zero.  A
+ * lookup steps over it (a free slot would cut the runs of the keys behind it);
+ * an insert may reuse it.  Only ever a slot's kind, never an xlat record's. */
+#define MOSRX_NAT_TOMB 0xFFu
+enum { MOSRX_NAT_OP_ADD = 1, MOSRX_NAT_OP_DEL = 2 };
+/* One change: ADD the binding b under the id `bind` (any but MOSRX_NAT_NO_BIND;
+ * it is what xlat.bind reports), or DEL the binding b (all of it named; bind is
+ * not read). */
+typedef struct mosrx_nat_op {
+	mosrx_nat_binding b;
+	uint32_t op;
+	uint32_t bind;
+} mosrx_nat_op;
+/* The final image of one slot that a list of ops changed. */
+typedef struct mosrx_nat_touch {
+	uint32_t slot, pad[3];
+	mosrx_nat_slot image;
+} mosrx_nat_touch;
+/* What the arithmetic keeps about a table: its slots (a power of two), its live
+ * keys (two a binding), its tombstones, and the loop bound.  Of a table from
+ * mosrx_nat_build: {mosrx_nat_slots(n), 2 * n, 0, *probe}. */
+typedef struct mosrx_nat_tstate {
+	uint32_t slots, keys, tombs, probe;
+} mosrx_nat_tstate;
+/* Apply ops[0 .. n) in their order to the host table slots[st->slots] and return
+ * in touch[4 * n] the final image of every slot that changed: one entry a slot
+ * (the last write wins), slots ascending; *ntouch of them.  No GPU needed.
+ *   ADD  both keys go in as mosrx_nat_build puts them: the walk from the key's
+ *        hash first finds the key absent up to a free slot, then the key takes
+ *        the first tombstone that walk passed, or else the free slot.  probe
+ *        grows to the new key's distance and never shrinks.
+ *   DEL  both keys must be there with one common bind; both slots become
+ *        tombstones.
+ * A refused call leaves slots and *st byte for byte as they were:
+ *   -EINVAL  NULL arguments or a state that is no table's, an op that is neither,
+ *            a zero nat_ip or nat_port, bind == MOSRX_NAT_NO_BIND, or more than
+ *            MOSRX_NAT_MAX_BINDINGS live bindings;
+ *   -EEXIST  an ADD one of whose keys is live;
+ *   -ENOENT  a DEL of a binding that is not there;
+ *   -ENOSPC  keys + tombs would pass half of the slots (mosrx_nat_build's "at
+ *            most half full" with the tombstones counted: what keeps runs short
+ *            and every walk ending at a free slot): rebuild. */
+int  mosrx_nat_apply(mosrx_nat_slot *slots, mosrx_nat_tstate *st, const mosrx_nat_op *ops, uint32_t n,
+                     mosrx_nat_touch *touch, uint32_t *ntouch);
+/* The ops applied to the installed table where it lies: mosrx_nat_apply on the
+ * context's host mirror of it, then one small launch on `stream` (NULL: the
+ * context's own) that stores the changed slots into the installed device copy.
+ * ops is dead on return; the device may apply it later, in stream order:
+ *   - a launch submitted to that stream before this call reads the old table,
+ *     one submitted after it the new one;
+ *   - the update waits (on the device, not the host) for every plan-nat launch
+ *     the context made on another stream before this call, and for the update
+ *     before it;
+ *   - launches made on another stream after it are the caller's to order.
+ * When the arithmetic answers -ENOSPC the call rebuilds instead: the live
+ * bindings and the ops into a fresh table of mosrx_nat_slots(live) slots without
+ * tombstones, every bind id kept, installed as mosrx_nat_set installs one (the
+ * pool's next copy, a blocking upload, its drain rule).  Either way one call and
+ * 0.  Any other refusal (mosrx_nat_apply's, in its terms) leaves the mirror, the
+ * device table and the stats as they were and launches nothing.  A context whose
+ * table was never set starts from the empty one.  mosrx_nat_set resets the ids to
+ * the array's indices.  n == 0: 0, nothing done; n over
+ * MOSRX_NAT_UPDATE_MAX_OPS (every port of the pool released and assigned once):
+ * -EINVAL.
+ * Where the host does wait: for the launch that last read the staging buffer, once
+ * four updates are outstanding; in mosrx__drain's place when more callers' streams
+ * than the context tracks have run plan-nat; and in the rebuild's blocking upload.
+ * Should the launch itself fail in the runtime (-EIO) the mirror is ahead of the
+ * device copy until the next mosrx_nat_set; every failure before it leaves both
+ * as they were. */
+#define MOSRX_NAT_UPDATE_MAX_OPS (2u * MOSRX_NAT_MAX_BINDINGS)
+int  mosrx_nat_update(mosrx_ctx *c, const mosrx_nat_op *ops, uint32_t n, void *stream);
+typedef struct mosrx_nat_stats {
+	uint32_t live, tombs, slots, probe;   /* bindings, tombstones, slots and the loop bound of the installed table */
+	uint64_t updates, rebuilds;           /* successful mosrx_nat_update calls; those of them that rebuilt */
+} mosrx_nat_stats;
+int  mosrx_nat_get_stats(const mosrx_ctx *c, mosrx_nat_stats *out);
 
 /* One launch in place of mosrx_fwd_plan_dev (same arguments, same plan for every
  * frame that is not translated).  A frame is eligible when its reason is TCP_OK,

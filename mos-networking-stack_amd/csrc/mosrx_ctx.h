@@ -206,6 +206,30 @@ struct mosrx_ctx {
 	int nat_pool_used[MOSRX_NAT_POOL];
 	uint32_t nat_pool_next;
 	uint32_t nat_n, nat_mask, nat_probe;   /* the installed table: bindings, slots - 1, the longest probe run */
+	/* ... and its host mirror (mosrx_nat_update): the table as it was built and
+	 * changed since, which also holds the live bindings and their ids */
+	mosrx_nat_slot *nat_h;
+	mosrx_nat_tstate nat_st;
+	uint64_t nat_updates, nat_rebuilds;
+	/* the touch lists of the last MOSRX_NAT_STAGE updates, pinned and read by the
+	 * update launch where they lie (d: the device address); ev is recorded behind
+	 * that launch, and a buffer is written again only after its event (busy) */
+#define MOSRX_NAT_STAGE 4
+	struct {
+		mosrx_nat_touch *h;
+		const mosrx_nat_touch *d;
+		uint32_t cap;
+		hipEvent_t ev;
+		hipStream_t stream;
+		int busy;
+	} nat_stage[MOSRX_NAT_STAGE];
+	uint32_t nat_stage_next;
+	/* the context's own streams a plan-nat launch went to since the last update
+	 * (bit 0: stream, 1 ..: the slots', then xs[]), and an event for each: the
+	 * update's stream waits for them (callers' streams: fev[], above) */
+#define MOSRX_NAT_OWN (1 + NSLOT + MOSRX_MAX_STREAMS)
+	uint32_t nat_own_mask;
+	hipEvent_t nat_own_ev[MOSRX_NAT_OWN];
 };
 
 /* ---- batch queue (one launch over many resident batches) ---- */

@@ -1,6 +1,7 @@
 /*
- * mosrx_nat.h — shared between the C host library (nat_api.c), the NAT kernels
- * (mosrx_nat.hip) and the stand-alone checksum driver (tests/csrc/nat_csum_driver.c).
+ * mosrx_nat.h — shared between the C host library (nat_api.c, nat_table.c), the
+ * NAT kernels (mosrx_nat.hip) and the stand-alone drivers (tests/csrc/nat_csum_driver.c,
+ * tests/csrc/nat_update_driver.c).
  * Plain C layout; the arithmetic below compiles for the host and the device.
  */
 #ifndef MOSRX_NAT_H
@@ -123,6 +124,23 @@ typedef struct mosrx_npatch {
  * do (n == 0, a queue of empty batches) launches nothing. */
 int mosrx_launch_nat_plan(const mosrx_nparams *np, void *stream);
 int mosrx_launch_nat_patch(const mosrx_npatch *pp, void *stream);
+/* update: lane i of ceil(m / 256) workgroups stores touch[i].image into
+ * slots[touch[i].slot] when that slot is <= mask, as two 16-byte stores; the
+ * host made the slots distinct (mosrx_nat_apply), so no two lanes meet.  touch
+ * may be pinned host memory, by its device address.  -EINVAL, before any launch,
+ * for a NULL or misaligned (16) table or touch array and for a mask that is not
+ * 2^k - 1 or is below MOSRX_NAT_MIN_SLOTS - 1. */
+int mosrx_launch_nat_update(mosrx_nat_slot *slots, uint32_t mask, const mosrx_nat_touch *touch, uint32_t m, void *stream);
+
+/* ---- the table's arithmetic (nat_table.c), as nat_api.c reaches it ------------------- */
+/* mosrx_nat_build with binding i's id ids[i] (NULL: i), into a table of cap slots
+ * (0: mosrx_nat_slots(n), and no fewer; a power of two). */
+int mosrx__nat_build_ids(const mosrx_nat_binding *b, const uint32_t *ids, uint32_t n, mosrx_nat_slot *slots, uint32_t cap,
+                         uint32_t *probe);
+/* The live bindings of a table and their ids, in slot order of their client-side
+ * keys, into b[max] / ids[max]; returns how many there are (more than max: only
+ * max were written). */
+uint32_t mosrx__nat_live(const mosrx_nat_slot *slots, uint32_t nslots, mosrx_nat_binding *b, uint32_t *ids, uint32_t max);
 
 #ifdef __cplusplus
 }

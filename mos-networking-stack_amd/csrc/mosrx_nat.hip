@@ -27,6 +27,11 @@
 //             ring's written run whose frame was translated gets its four fields
 //             stored into the built frame (2- and 4-byte stores: ring frames sit
 //             at 16 k + 2).
+//   update    one lane per changed slot of the table (mosrx_nat_update): the
+//             host did the table's arithmetic and made the slots distinct; a
+//             lane stores one 32-byte image.  No loop, no LDS, no atomics.
+// A slot whose kind is MOSRX_NAT_TOMB held a key that was deleted: the lookup
+// steps over it, where a free slot ends the run.
 // No workgroup waits on another; every loop's bound (the table sizes, probe,
 // ihl <= 15, nrings <= 16, the queue's batch search) is known at its entry;
 // every frame read goes through the buffer resource; every per-frame store sits
@@ -48,6 +53,7 @@ static_assert(offsetof(mosrx_nat_slot, port) == 12 && offsetof(mosrx_nat_slot, k
 static_assert(offsetof(mosrx_nat_xlat, port) == 4 && offsetof(mosrx_nat_xlat, ip_check) == 6 &&
               offsetof(mosrx_nat_xlat, tcp_check) == 8 && offsetof(mosrx_nat_xlat, kind) == 10 &&
               offsetof(mosrx_nat_xlat, ihl) == 11 && offsetof(mosrx_nat_xlat, bind) == 12, "xlat dwords");
+static_assert(sizeof(mosrx_nat_touch) == 48 && offsetof(mosrx_nat_touch, image) == 16, "a touch entry: three 16-byte loads");
 
 // bytes a .. a+3 of the batch buffer, any alignment (zero past its end); the name
 // mosrx_fwd_plan_body.inc calls
@@ -119,7 +125,7 @@ __device__ __forceinline__ void nat_plan_body(const mosrx_fparams p, const mosrx
 			const u32x4 k = *reinterpret_cast<const u32x4 *>(s);
 			const uint32_t sk = (k.w >> 16) & 0xFFu;
 			if (sk != MOSRX_NAT_SNAT && sk != MOSRX_NAT_DNAT) {
-				looking = false;                                // a free slot ends the run: no binding
+				looking = sk == MOSRX_NAT_TOMB;                 // a free slot ends the run: no binding; a deleted key's is stepped over
 			} else if (k.x == k_sa && k.y == k_da && k.z == k_pt) {
 				const u32x2 val = *reinterpret_cast<const u32x2 *>(&s->addr);
 				x_kind = sk;
@@ -265,7 +271,40 @@ __global__ __launch_bounds__(MOSRX_NAT_THREADS) void mosrx_nat_patch_queue_kerne
 	nat_patch_body(pp.xtab[k], d.tx, d.tx_off, d.tx_src, d.rings, pp.nrings, d.n, blockIdx.x - d.tile_base);
 }
 
+// ---- update ------------------------------------------------------------------
+// Lane i stores the image of touch[i] into its slot: three 16-byte loads (the
+// slot index, the image's halves), two 16-byte stores under i < m and slot <= mask.
+// The value half goes first and the key half, which holds the kind, behind it;
+// the ordering that counts is the stream's (include/mosrx.h mosrx_nat_update).
+__global__ __launch_bounds__(MOSRX_NAT_THREADS) void mosrx_nat_update_kernel(mosrx_nat_slot *slots, uint32_t mask,
+                                                                            const mosrx_nat_touch *touch, uint32_t m)
+{
+	const uint32_t i = blockIdx.x * MOSRX_NAT_THREADS + threadIdx.x;
+	if (i >= m)
+		return;
+	const u32x4 *t = reinterpret_cast<const u32x4 *>(touch + i);
+	const u32x4 hd = t[0], key = t[1], val = t[2];
+	if (hd.x > mask)
+		return;
+	u32x4 *s = reinterpret_cast<u32x4 *>(slots + hd.x);
+	s[1] = val;
+	s[0] = key;
+}
+
 // ---- launches ----------------------------------------------------------------
+extern "C" int mosrx_launch_nat_update(mosrx_nat_slot *slots, uint32_t mask, const mosrx_nat_touch *touch, uint32_t m,
+                                       void *stream)
+{
+	if (!slots || ((uintptr_t)slots & 15) || !touch || ((uintptr_t)touch & 15) || (mask & (mask + 1u)) ||
+	    mask + 1u < MOSRX_NAT_MIN_SLOTS)
+		return -EINVAL;
+	if (m == 0)
+		return 0;
+	hipLaunchKernelGGL(mosrx_nat_update_kernel, dim3((m + MOSRX_NAT_THREADS - 1u) / MOSRX_NAT_THREADS),
+	                   dim3(MOSRX_NAT_THREADS), 0, (hipStream_t)stream, slots, mask, touch, m);
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
 extern "C" int mosrx_launch_nat_plan(const mosrx_nparams *np, void *stream)
 {
 	const hipStream_t s = (hipStream_t)stream;

@@ -19,112 +19,35 @@ static int aligned(const void *p, uintptr_t a)
 	return p && !((uintptr_t)p & (a - 1));
 }
 
-/* ---- the table ------------------------------------------------------------------- */
-
-uint32_t mosrx_nat_hash(uint32_t saddr, uint32_t daddr, uint32_t ports)
-{
-	return mosrx_nat_hash_key(saddr, daddr, ports);
-}
-
-uint32_t mosrx_nat_slots(uint32_t n)
-{
-	uint32_t cap = MOSRX_NAT_MIN_SLOTS;
-	if (n > MOSRX_NAT_MAX_BINDINGS)
-		n = MOSRX_NAT_MAX_BINDINGS;
-	while (cap < 4u * n)
-		cap <<= 1;
-	return cap;
-}
-
-/* One key into the table: 0, or -EINVAL when it is there already.  *probe grows
- * to the slots this key's lookup examines. */
-static int nat_insert(mosrx_nat_slot *slots, uint32_t mask, uint32_t sa, uint32_t da, uint32_t pt, uint8_t kind,
-                      uint32_t addr, uint16_t port, uint32_t bind, uint32_t *probe)
-{
-	const uint32_t h = mosrx_nat_hash_key(sa, da, pt);
-	uint32_t d;
-	for (d = 0; d <= mask; d++) {   /* (at most half full: a free slot comes) */
-		mosrx_nat_slot *s = &slots[(h + d) & mask];
-		if (!s->kind) {
-			s->saddr = sa;
-			s->daddr = da;
-			s->ports = pt;
-			s->port = port;
-			s->kind = kind;
-			s->addr = addr;
-			s->bind = bind;
-			if (d + 1 > *probe)
-				*probe = d + 1;
-			return 0;
-		}
-		if (s->saddr == sa && s->daddr == da && s->ports == pt)
-			return -EINVAL;
-	}
-	return -EINVAL;
-}
-
-int mosrx_nat_build(const mosrx_nat_binding *b, uint32_t n, mosrx_nat_slot *slots, uint32_t *probe)
-{
-	uint32_t i, run = 0, mask;
-	if (n > MOSRX_NAT_MAX_BINDINGS || (n && !b) || !slots)
-		return -EINVAL;
-	mask = mosrx_nat_slots(n) - 1;
-	memset(slots, 0, ((size_t)mask + 1) * sizeof(*slots));
-	for (i = 0; i < n; i++) {
-		const mosrx_nat_binding *x = &b[i];
-		if (!x->nat_ip || !x->nat_port)
-			return -EINVAL;
-		/* client side: the frame the client sent; server side: the server's answer to the NAT's address */
-		if (nat_insert(slots, mask, x->cli_ip, x->svr_ip, (uint32_t)x->cli_port | (uint32_t)x->svr_port << 16,
-		               MOSRX_NAT_SNAT, x->nat_ip, x->nat_port, i, &run) ||
-		    nat_insert(slots, mask, x->svr_ip, x->nat_ip, (uint32_t)x->svr_port | (uint32_t)x->nat_port << 16,
-		               MOSRX_NAT_DNAT, x->cli_ip, x->cli_port, i, &run))
-			return -EINVAL;
-	}
-	if (probe)
-		*probe = run;
-	return 0;
-}
-
-int mosrx_nat_check(const mosrx_nat_binding *b, uint32_t n)
-{
-	mosrx_nat_slot *slots;
-	int rc;
-	if (n > MOSRX_NAT_MAX_BINDINGS || (n && !b))
-		return -EINVAL;
-	if (!(slots = malloc((size_t)mosrx_nat_slots(n) * sizeof(*slots))))
-		return -ENOMEM;
-	rc = mosrx_nat_build(b, n, slots, NULL);
-	free(slots);
-	return rc;
-}
+/* ---- the table (its arithmetic: nat_table.c) ---------------------------------------- */
 
 uint32_t mosrx_nat_count(const mosrx_ctx *c) { return c ? c->nat_n : 0; }
 
-/* The table goes to the next buffer of a pool, as the forwarding tables do
- * (fwd_api.c mosrx_fwd_set): launches submitted earlier may still read the copy
- * they were given, so a buffer is written again (or freed to grow) only after
- * those launches drained, and only if a launch may have read it since its last
- * write. */
-int mosrx_nat_set(mosrx_ctx *c, const mosrx_nat_binding *b, uint32_t n)
+int mosrx_nat_get_stats(const mosrx_ctx *c, mosrx_nat_stats *out)
 {
-	mosrx_nat_slot *h;
-	uint32_t k, probe = 0, cap;
-	size_t bytes;
-	int rc;
-	if (!c || n > MOSRX_NAT_MAX_BINDINGS || (n && !b))
+	if (!c || !out)
 		return -EINVAL;
-	if (!b)
-		n = 0;
-	cap = mosrx_nat_slots(n);
-	bytes = (size_t)cap * sizeof(*h);
-	if (!(h = malloc(bytes)))
-		return -ENOMEM;
-	if ((rc = mosrx_nat_build(b, n, h, &probe))) {
-		free(h);
-		return rc;
-	}
-	k = c->nat_pool_next;
+	memset(out, 0, sizeof(*out));
+	out->live = c->nat_n;
+	out->tombs = c->nat_st.tombs;
+	out->slots = c->d_nat ? c->nat_mask + 1 : 0;
+	out->probe = c->nat_probe;
+	out->updates = c->nat_updates;
+	out->rebuilds = c->nat_rebuilds;
+	return 0;
+}
+
+/* The host table h (cap slots, n bindings, no tombstones; the context's from
+ * here on success) goes to the next buffer of a pool, as the forwarding tables
+ * do (fwd_api.c mosrx_fwd_set): launches submitted earlier may still read or
+ * update the copy they were given, so a buffer is written again (or freed to
+ * grow) only after those launches drained, and only if a launch may have touched
+ * it since its last write. */
+static int nat_install(mosrx_ctx *c, mosrx_nat_slot *h, uint32_t cap, uint32_t n, uint32_t probe)
+{
+	const size_t bytes = (size_t)cap * sizeof(*h);
+	const uint32_t k = c->nat_pool_next;
+	int rc = 0;
 	if (hipSetDevice(c->device) != hipSuccess)
 		rc = -EIO;
 	if (!rc && c->nat_pool_used[k] && !(rc = mosrx__drain(c)))
@@ -143,7 +66,6 @@ int mosrx_nat_set(mosrx_ctx *c, const mosrx_nat_binding *b, uint32_t n)
 	}
 	if (!rc && hipMemcpy(c->d_nat_pool[k], h, bytes, hipMemcpyHostToDevice) != hipSuccess)
 		rc = -EIO;
-	free(h);
 	if (rc)
 		return rc;
 	c->d_nat = c->d_nat_pool[k];
@@ -151,7 +73,30 @@ int mosrx_nat_set(mosrx_ctx *c, const mosrx_nat_binding *b, uint32_t n)
 	c->nat_mask = cap - 1;
 	c->nat_probe = probe;
 	c->nat_pool_next = (k + 1) % MOSRX_NAT_POOL;
+	free(c->nat_h);
+	c->nat_h = h;
+	c->nat_st.slots = cap;
+	c->nat_st.keys = 2 * n;
+	c->nat_st.tombs = 0;
+	c->nat_st.probe = probe;
 	return 0;
+}
+
+int mosrx_nat_set(mosrx_ctx *c, const mosrx_nat_binding *b, uint32_t n)
+{
+	mosrx_nat_slot *h;
+	uint32_t probe = 0, cap;
+	int rc;
+	if (!c || n > MOSRX_NAT_MAX_BINDINGS || (n && !b))
+		return -EINVAL;
+	if (!b)
+		n = 0;
+	cap = mosrx_nat_slots(n);
+	if (!(h = malloc((size_t)cap * sizeof(*h))))
+		return -ENOMEM;
+	if ((rc = mosrx_nat_build(b, n, h, &probe)) || (rc = nat_install(c, h, cap, n, probe)))
+		free(h);
+	return rc;
 }
 
 void mosrx__nat_free(mosrx_ctx *c)
@@ -160,13 +105,216 @@ void mosrx__nat_free(mosrx_ctx *c)
 	for (i = 0; i < MOSRX_NAT_POOL; i++)
 		if (c->d_nat_pool[i])
 			hipFree(c->d_nat_pool[i]);
+	for (i = 0; i < MOSRX_NAT_STAGE; i++) {
+		if (c->nat_stage[i].busy)
+			hipEventSynchronize(c->nat_stage[i].ev);
+		if (c->nat_stage[i].ev)
+			hipEventDestroy(c->nat_stage[i].ev);
+		if (c->nat_stage[i].h)
+			hipHostFree(c->nat_stage[i].h);
+	}
+	for (i = 0; i < MOSRX_NAT_OWN; i++)
+		if (c->nat_own_ev[i])
+			hipEventDestroy(c->nat_own_ev[i]);
+	free(c->nat_h);
 }
 
-/* A launch that reads the installed table is about to go to stream. */
-static void nat_mark_used(mosrx_ctx *c)
+/* The context's own stream number k (mosrx_ctx.h nat_own_mask), NULL past the last. */
+static hipStream_t nat_own_stream(const mosrx_ctx *c, uint32_t k)
 {
+	if (k == 0)
+		return c->stream;
+	if (k < 1 + NSLOT)
+		return c->slot[k - 1].stream;
+	return k - 1 - NSLOT < c->nxs ? c->xs[k - 1 - NSLOT] : NULL;
+}
+
+/* A launch that reads the installed table is about to go to stream s. */
+static void nat_mark_used(mosrx_ctx *c, hipStream_t s)
+{
+	uint32_t k;
 	c->nat_pool_used[(c->nat_pool_next + MOSRX_NAT_POOL - 1) % MOSRX_NAT_POOL] = 1;
 	mosrx__fwd_mark_used(c);
+	/* (a caller's stream: mosrx__note_stream records its event behind the launch) */
+	for (k = 0; k < MOSRX_NAT_OWN; k++)
+		if (s && s == nat_own_stream(c, k))
+			c->nat_own_mask |= 1u << k;
+}
+
+/* ---- bindings added and removed in place ------------------------------------------- */
+
+/* Stream s waits, on the device, for what an update must not overtake: the
+ * plan-nat launches made on other streams and the update before this one.  The
+ * callers' streams' events are those mosrx__note_stream recorded behind each
+ * launch; on the context's own streams an event is recorded now.  More callers'
+ * streams than the table holds: the host drains instead. */
+static int nat_order(mosrx_ctx *c, hipStream_t s)
+{
+	const uint32_t last = (c->nat_stage_next + MOSRX_NAT_STAGE - 1) % MOSRX_NAT_STAGE;
+	uint32_t k;
+	if (c->foreign_streams)
+		return mosrx__drain(c);
+	for (k = 0; k < c->nfs; k++)
+		if (c->fstream[k] != s)
+			HIPCHK(hipStreamWaitEvent(s, c->fev[k], 0));
+	for (k = 0; k < MOSRX_NAT_OWN; k++) {
+		const hipStream_t t = nat_own_stream(c, k);
+		if (!(c->nat_own_mask & 1u << k) || !t || t == s)
+			continue;
+		if (!c->nat_own_ev[k])
+			HIPCHK(hipEventCreateWithFlags(&c->nat_own_ev[k], hipEventDisableTiming));
+		HIPCHK(hipEventRecord(c->nat_own_ev[k], t));
+		HIPCHK(hipStreamWaitEvent(s, c->nat_own_ev[k], 0));
+	}
+	if (c->nat_stage[last].busy && c->nat_stage[last].stream != s)
+		HIPCHK(hipStreamWaitEvent(s, c->nat_stage[last].ev, 0));
+	return 0;
+}
+
+/* The staging buffer of the next update with room for `need` entries, free of
+ * the launch that read it last. */
+static int nat_stage_take(mosrx_ctx *c, uint32_t need, uint32_t *which)
+{
+	const uint32_t k = c->nat_stage_next;
+	if (c->nat_stage[k].busy) {
+		HIPCHK(hipEventSynchronize(c->nat_stage[k].ev));
+		c->nat_stage[k].busy = 0;
+	}
+	if (!c->nat_stage[k].ev)
+		HIPCHK(hipEventCreateWithFlags(&c->nat_stage[k].ev, hipEventDisableTiming));
+	if (c->nat_stage[k].cap < need) {
+		void *d = NULL;
+		uint32_t cap = 256;
+		while (cap < need)
+			cap <<= 1;
+		if (c->nat_stage[k].h)
+			hipHostFree(c->nat_stage[k].h);
+		c->nat_stage[k].h = NULL;
+		c->nat_stage[k].cap = 0;
+		if (hipHostMalloc((void **)&c->nat_stage[k].h, (size_t)cap * sizeof(mosrx_nat_touch), hipHostMallocDefault) != hipSuccess)
+			return -ENOMEM;
+		if (hipHostGetDevicePointer(&d, c->nat_stage[k].h, 0) != hipSuccess)
+			return -EIO;   /* (cap stays 0: the next call allocates again) */
+		c->nat_stage[k].d = (const mosrx_nat_touch *)d;
+		c->nat_stage[k].cap = cap;
+	}
+	*which = k;
+	return 0;
+}
+
+/* The table is too full of keys and tombstones for the ops: the live bindings
+ * and the ops into a fresh one.  The ops run, by mosrx_nat_apply and so under
+ * its refusals, on a scratch table with room for all of them; what is live
+ * there is then built without tombstones and installed.  Nothing of the context
+ * changes before the install. */
+static int nat_rebuild(mosrx_ctx *c, const mosrx_nat_op *ops, uint32_t n)
+{
+	const uint32_t live = c->nat_st.keys / 2;
+	uint32_t cap = MOSRX_NAT_MIN_SLOTS, m = 0, left, probe = 0, *ids = NULL;
+	mosrx_nat_binding *b = NULL;
+	mosrx_nat_slot *h = NULL, *scratch = NULL;
+	mosrx_nat_touch *touch = NULL;
+	mosrx_nat_tstate st;
+	int rc = -ENOMEM;
+	while (cap < 4u * (live + n))
+		cap <<= 1;
+	b = malloc(((size_t)live + n + 1) * sizeof(*b));
+	ids = malloc(((size_t)live + n + 1) * sizeof(*ids));
+	scratch = malloc((size_t)cap * sizeof(*scratch));
+	touch = malloc((size_t)4 * n * sizeof(*touch));
+	if (!b || !ids || !scratch || !touch)
+		goto out;
+	/* the live keys as they lie, without the tombstones, into the scratch table */
+	mosrx__nat_live(c->nat_h, c->nat_st.slots, b, ids, live);
+	if ((rc = mosrx__nat_build_ids(b, ids, live, scratch, cap, &probe)))
+		goto out;   /* (the mirror's own keys collide: not a table of ours) */
+	st.slots = cap;
+	st.keys = 2 * live;
+	st.tombs = 0;
+	st.probe = probe;
+	if ((rc = mosrx_nat_apply(scratch, &st, ops, n, touch, &m)))
+		goto out;
+	left = mosrx__nat_live(scratch, cap, b, ids, live + n);
+	rc = -ENOMEM;
+	if (!(h = malloc((size_t)mosrx_nat_slots(left) * sizeof(*h))))
+		goto out;
+	if ((rc = mosrx__nat_build_ids(b, ids, left, h, 0, &probe)) || (rc = nat_install(c, h, mosrx_nat_slots(left), left, probe)))
+		free(h);
+out:
+	free(b);
+	free(ids);
+	free(scratch);
+	free(touch);
+	return rc;
+}
+
+int mosrx_nat_update(mosrx_ctx *c, const mosrx_nat_op *ops, uint32_t n, void *stream)
+{
+	mosrx_nat_tstate st;
+	hipStream_t s;
+	uint32_t k, m = 0;
+	int rc;
+	if (!c || (n && !ops) || n > MOSRX_NAT_UPDATE_MAX_OPS)
+		return -EINVAL;
+	if (n == 0)
+		return 0;
+	HIPCHK(hipSetDevice(c->device));
+	if (!c->d_nat) {
+		/* never set: the empty table, installed once every op is known to be acceptable to it -- tried on a
+		 * scratch table with room for all of them (each op adds at most two keys or tombstones) */
+		uint32_t cap = MOSRX_NAT_MIN_SLOTS;
+		mosrx_nat_slot *scratch;
+		mosrx_nat_touch *t;
+		while (cap < 4u * n)
+			cap <<= 1;
+		scratch = calloc(cap, sizeof(*scratch));
+		t = malloc((size_t)4 * n * sizeof(*t));
+		rc = -ENOMEM;
+		if (scratch && t) {
+			st.slots = cap;
+			st.keys = st.tombs = st.probe = 0;
+			rc = mosrx_nat_apply(scratch, &st, ops, n, t, &m);
+		}
+		free(scratch);
+		free(t);
+		if (rc || (rc = mosrx_nat_set(c, NULL, 0)))
+			return rc;
+	}
+	s = stream ? (hipStream_t)stream : c->stream;
+	/* what can fail in the runtime comes before the mirror changes: the staging buffer, the waits */
+	if ((rc = nat_stage_take(c, 4u * n, &k)) || (rc = nat_order(c, s)))
+		return rc;
+	st = c->nat_st;
+	rc = mosrx_nat_apply(c->nat_h, &st, ops, n, c->nat_stage[k].h, &m);
+	if (rc == -ENOSPC) {
+		if (!(rc = nat_rebuild(c, ops, n))) {
+			c->nat_updates++;
+			c->nat_rebuilds++;
+		}
+		return rc;
+	}
+	if (rc)
+		return rc;
+	/* The mirror has changed.  Should the launch itself fail (-EIO: the runtime's) the device copy stays
+	 * behind it; mosrx_nat_set installs a whole table again. */
+	c->nat_st = st;
+	c->nat_n = st.keys / 2;
+	c->nat_probe = st.probe;
+	c->nat_pool_used[(c->nat_pool_next + MOSRX_NAT_POOL - 1) % MOSRX_NAT_POOL] = 1;
+	if ((rc = mosrx_launch_nat_update(c->d_nat, c->nat_mask, c->nat_stage[k].d, m, (void *)s)))
+		return rc;
+	c->nat_updates++;
+	c->nat_own_mask = 0;
+	mosrx__note_stream(c, s);   /* (a caller's stream: the drain ahead of this copy's next rewrite waits for it) */
+	if (hipEventRecord(c->nat_stage[k].ev, s) != hipSuccess) {
+		/* no event to tell when the launch has read the buffer: wait for it here */
+		HIPCHK(hipStreamSynchronize(s));
+		return 0;
+	}
+	c->nat_stage[k].busy = 1;
+	c->nat_stage[k].stream = s;
+	c->nat_stage_next = (k + 1) % MOSRX_NAT_STAGE;
+	return 0;
 }
 
 /* What plan-nat takes from the context: the installed tables of both kinds and
@@ -233,7 +381,7 @@ int mosrx_fwd_plan_nat_dev(mosrx_ctx *c, const mosrx_batch *b, const void *d_rec
 	np.xlat = d_xlat;
 	s = stream ? (hipStream_t)stream : c->stream;
 	HIPCHK(hipSetDevice(c->device));
-	nat_mark_used(c);
+	nat_mark_used(c, s);
 	rc = mosrx_launch_nat_plan(&np, (void *)s);
 	mosrx__note_stream(c, s);   /* (after the launch: its event covers it) */
 	return rc;
@@ -284,7 +432,7 @@ int mosrx__nat_queue_launch_plan(mosrx_ctx *c, const mosrx_queue *q, void *strea
 	np.nb = q->nb;
 	np.total_tiles = q->fwd_tiles;
 	HIPCHK(hipSetDevice(c->device));
-	nat_mark_used(c);
+	nat_mark_used(c, s);
 	rc = mosrx_launch_nat_plan(&np, (void *)s);
 	mosrx__note_stream(c, s);
 	return rc;

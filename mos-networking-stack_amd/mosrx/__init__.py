@@ -11,6 +11,7 @@ GetRSSCPUCore outputs (core/src/util.c:61-131).
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -314,6 +315,59 @@ def nat_table(bindings: np.ndarray):
     _chk(lib().mosrx_nat_build(b.ctypes.data if len(b) else None, len(b), slots.ctypes.data, C.byref(probe)),
          "mosrx_nat_build")
     return slots, int(probe.value)
+
+
+NAT_TOMB = 0xFF                     # MOSRX_NAT_TOMB: a slot whose key was deleted (a slot's kind only)
+NAT_OP_ADD, NAT_OP_DEL = 1, 2       # MOSRX_NAT_OP_*
+NAT_UPDATE_MAX_OPS = 2 * NAT_MAX_BINDINGS   # MOSRX_NAT_UPDATE_MAX_OPS: more ops in one nat_update are refused
+NAT_OP_DTYPE = np.dtype([("b", NAT_BINDING_DTYPE), ("op", "<u4"), ("bind", "<u4")])
+NAT_TOUCH_DTYPE = np.dtype([("slot", "<u4"), ("pad", "<u4", 3), ("image", NAT_SLOT_DTYPE)])
+NAT_STATS_DTYPE = np.dtype([("live", "<u4"), ("tombs", "<u4"), ("slots", "<u4"), ("probe", "<u4"), ("updates", "<u8"),
+                            ("rebuilds", "<u8")])
+assert NAT_OP_DTYPE.itemsize == 28 and NAT_TOUCH_DTYPE.itemsize == 48 and NAT_STATS_DTYPE.itemsize == 32
+NatState = collections.namedtuple("NatState", "slots keys tombs probe")    # mosrx_nat_tstate
+NatStats = collections.namedtuple("NatStats", "live tombs slots probe updates rebuilds")
+
+
+def nat_ops(adds=(), dels=(), nat_ip: str = None) -> np.ndarray:
+    """NAT_OP_DTYPE records for mosrx_nat_update / mosrx_nat_apply: the deletes first,
+    in their order, then the adds in theirs (so a flow may be deleted and bound again
+    in one call).  adds: [(flow, bind), ...], dels: [flow, ...]; a flow is nat_bindings'
+    tuple (cli_ip, cli_port, svr_ip, svr_port, nat_port) or one NAT_BINDING_DTYPE
+    record (nat_ip then not needed)."""
+    def rec(f):
+        if isinstance(f, (np.void, np.ndarray)):
+            return np.asarray(f, NAT_BINDING_DTYPE).reshape(())
+        return nat_bindings([f], nat_ip)[0]
+    out = np.zeros(len(dels) + len(adds), NAT_OP_DTYPE)
+    for i, f in enumerate(dels):
+        out[i]["b"], out[i]["op"] = rec(f), NAT_OP_DEL
+    for i, (f, bind) in enumerate(adds, len(dels)):
+        out[i]["b"], out[i]["op"], out[i]["bind"] = rec(f), NAT_OP_ADD, bind
+    return out
+
+
+def nat_state(slots: np.ndarray, probe: int) -> NatState:
+    """The NatState of a table as nat_table returns it (or as nat_apply left it)."""
+    k = slots["kind"]
+    return NatState(len(slots), int(((k == NAT_SNAT) | (k == NAT_DNAT)).sum()), int((k == NAT_TOMB).sum()), int(probe))
+
+
+def nat_apply(slots: np.ndarray, state, ops):
+    """mosrx_nat_apply: the ops applied in their order to the host table `slots` (a
+    contiguous NAT_SLOT_DTYPE array, changed in place) whose NatState is `state`;
+    returns (touch, the new NatState) -- touch the final image of every slot that
+    changed, NAT_TOUCH_DTYPE, slots ascending.  Raises MosrxError on a refusal, the
+    table then as it was."""
+    if slots.dtype != NAT_SLOT_DTYPE or not slots.flags.c_contiguous or not slots.flags.writeable:
+        raise ValueError("slots: a writable contiguous NAT_SLOT_DTYPE array")
+    o = np.ascontiguousarray(ops, NAT_OP_DTYPE)
+    st = np.array(tuple(state), np.uint32)
+    touch = np.zeros(4 * len(o), NAT_TOUCH_DTYPE)
+    m = C.c_uint32()
+    _chk(lib().mosrx_nat_apply(slots.ctypes.data, st.ctypes.data, o.ctypes.data if len(o) else None, len(o),
+                               touch.ctypes.data if len(o) else None, C.byref(m)), "mosrx_nat_apply")
+    return touch[:m.value].copy(), NatState(*(int(v) for v in st))
 
 
 def nat_patch_frame(frame, xlat) -> np.ndarray:
@@ -631,6 +685,10 @@ def lib():
             "mosrx_nat_check": (I, [P, U32]),
             "mosrx_nat_set": (I, [P, P, U32]),
             "mosrx_nat_count": (U32, [P]),
+            "mosrx_nat_apply": (I, [P, P, P, U32, P, C.POINTER(U32)]),
+            "mosrx_nat_update": (I, [P, P, U32, P]),
+            "mosrx_nat_get_stats": (I, [P, P]),
+            "mosrx_launch_nat_update": (I, [P, U32, P, U32, P]),
             "mosrx_fwd_plan_nat_dev": (I, [P, C.POINTER(Batch), P, I, I, P, P, P]),
             "mosrx_nat_patch_rings_dev": (I, [P, P, P, P, P, P, U32, U32, P]),
             "mosrx_nat_patch_frame": (None, [P, P]),
@@ -1217,6 +1275,20 @@ class Context:
 
     def nat_count(self) -> int:
         return int(lib().mosrx_nat_count(self.handle))
+
+    def nat_update(self, ops, stream: int = 0) -> None:
+        """mosrx_nat_update: NAT_OP_DTYPE records (nat_ops) applied to the installed table
+        in place, in `stream`'s order (0: the context's own stream); returns before the
+        device has applied them.  A table too full of tombstones is rebuilt instead."""
+        o = np.ascontiguousarray(ops, NAT_OP_DTYPE)
+        _chk(lib().mosrx_nat_update(self.handle, o.ctypes.data if len(o) else None, len(o), stream), "mosrx_nat_update")
+
+    def nat_stats(self) -> NatStats:
+        """mosrx_nat_get_stats: live bindings, tombstones, slots and loop bound of the
+        installed table; successful nat_update calls and those that rebuilt."""
+        st = np.zeros(1, NAT_STATS_DTYPE)
+        _chk(lib().mosrx_nat_get_stats(self.handle, st.ctypes.data), "mosrx_nat_get_stats")
+        return NatStats(*(int(v) for v in st[0]))
 
     def fwd_plan_nat_dev(self, b: Batch, d_rec: int, rec_bytes: int, in_ifidx: int, d_plan: int, d_xlat: int,
                          sync: bool = True, stream: int | None = None) -> None:
